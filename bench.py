@@ -3,7 +3,19 @@
 (16384^2 cells) on MI355X, plus the finest-level pass's HBM roofline fraction.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--reps R] [--n 16385]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline figure needs and no more: it creates one context (and
+runs its first W + min(K, 20) cycles untimed: setting up), sets the problem, runs W untimed
+warmup cycles, times K cycles in ONE call, writes its outputs if
+--dump-outputs DIR is given (phi after the timed call, or a fixed seeded sample of it, and
+the sweep counts, as DIR/*.npy; see dump_outputs), and prints the line (`value`,
+`ms_per_step`; `parity`, `roofline` and the other legs null or absent, `full`: false).
+Everything else described below -- 5 repetitions instead of 1, the hash check against the
+reference (`parity`), the per-pass roofline repetitions, the rocprofv3 PMC and trace children,
+the CPU baselines, the other configs, grids, precisions' and entry points' legs -- runs only
+with --full, each leg then by its own auto/off option.
 
 `--gpus N` with N > 1 outside a launcher (no WORLD_SIZE in the environment) starts N rank
 processes itself -- `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
@@ -17,10 +29,10 @@ the per-sweep residual-norm early exit, full-weighting restriction, the referenc
 prolongation, recursion to N=5) on the synthetic problem the reference itself solves:
 phi0 = 0, f = analytic RHS.  Inputs are resident in HBM before the timed region.
 
-Each of R repetitions (default 5) restarts from phi0 = 0 (set_problem, outside the timed
+Each of R repetitions (default 1; --full: 5) restarts from phi0 = 0 (set_problem, outside the timed
 region), runs W untimed warmup cycles, then times exactly K cycles in ONE call, bracketed
 by barrier + device sync on both sides, max over ranks.  `value` = K / the median time.
-After every repetition phi's FNV-64 hash (pgmg_solution_hash) is compared with the
+With --full, after every repetition phi's FNV-64 hash (pgmg_solution_hash) is compared with the
 reference's hash after W+K cycles (tests/golden/cycles.json, a fixture of the compiled
 reference's own runs): `parity` is true only when every repetition matched.
 
@@ -54,6 +66,12 @@ INST_REPS = 3             # repetitions with per-pass events (the roofline's eve
 PASSES = (0, 1, 2, 3, 4, 5)  # finest-level passes: sweep, k_pre, k_post, k_postpre, carry pass,
                              # recompute form
 METRIC = "V-cycles/sec + fine-grid stencil HBM GB/s, 2D Poisson N=16384², fp64"
+# the legs of the study that run only under --full (each then by its own auto/off option)
+FULL_LEGS = ("cpu_baseline", "general_rhs", "pmc", "other_configs", "big_grid", "fast_mode",
+             "dropin", "ops", "trace")
+PRIME_STEPS = 20            # a plain run's context runs at most this many cycles (+ warmup) first
+DUMP_MAX_BYTES = 48 << 20   # --dump-outputs: phi above this is written as a seeded sample
+DUMP_SEED = 20240517
 
 
 def parse():
@@ -61,7 +79,19 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--reps", type=int, default=5, help="timed repetitions (median reported)")
+    ap.add_argument("--reps", type=int, default=None,
+                    help="timed repetitions, each W warmup + K timed cycles from phi0 = 0 (the "
+                         "median is reported); default 1, with --full 5")
+    ap.add_argument("--full", action="store_true",
+                    help="the whole study beside the headline figure: 5 repetitions, the "
+                         "reference-hash check (parity), the per-pass roofline repetitions, and "
+                         "every leg that its own option below leaves on `auto` (CPU baselines, "
+                         "PMC and trace passes, other configs and grids, general RHS, FAST mode, "
+                         "drop-in, per-op study, RCCL latency floor).  Without it none of them runs")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed call left -- phi "
+                         "(a fixed seeded sample of it above 48 MB) and the sweep / early-exit "
+                         "counts -- as DIR/<name>.npy (float64)")
     ap.add_argument("--n", "--N", dest="n", type=int, default=16385,
                     help="points per side (2^k+1); --N under torch.distributed.run")
     ap.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto")
@@ -103,7 +133,37 @@ def parse():
                     help="directory to keep the rocprofv3 summaries of the trace and PMC passes")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--trace-child", action="store_true", help=argparse.SUPPRESS)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:   # a plain run: set up, warm up, time the steps, print the line
+        for leg in FULL_LEGS:
+            setattr(args, leg, "off")
+    if args.reps is None:
+        args.reps = 5 if args.full else 1
+    return args
+
+
+def dump_outputs(s, where, rank=0, world=1):
+    """--dump-outputs: what a caller of the timed path holds after its last timed call, as
+    float64 .npy files on rank 0: phi (pgmg_get_solution; on row strips gathered to rank 0) as
+    phi.npy, or above DUMP_MAX_BYTES as phi_sample.npy, its values at DUMP_MAX_BYTES / 8 flat
+    indices drawn once from numpy's default_rng(DUMP_SEED) and sorted (the same indices in
+    every run at the same N); stats.npy holds the context's sweep and early-exit counts
+    (pgmg_stats)."""
+    import numpy as np
+    phi = s.solution() if world == 1 else s.gather_solution(0, rank == 0)
+    sweeps, exits = s.stats()
+    if rank != 0:
+        return
+    d = pathlib.Path(where)
+    d.mkdir(parents=True, exist_ok=True)
+    flat = phi.reshape(-1)
+    name = "phi.npy"
+    if flat.nbytes > DUMP_MAX_BYTES:
+        idx = np.random.default_rng(DUMP_SEED).integers(0, flat.size, DUMP_MAX_BYTES // 8)
+        idx.sort()
+        flat, name = flat[idx], "phi_sample.npy"
+    np.save(d / name, np.ascontiguousarray(flat, dtype=np.float64))
+    np.save(d / "stats.npy", np.array([sweeps, exits], dtype=np.float64))
 
 
 def _cpu_model():
@@ -395,7 +455,7 @@ def live_trace(args):
     d = tempfile.mkdtemp(prefix="pgmg_trace_")
     cmd = ["timeout", "-s", "KILL", "300", prof, "--kernel-trace", "--stats", "--output-format",
            "csv", "-d", d, "-o", "run", "--", sys.executable, str(ROOT / "bench.py"),
-           "--trace-child", "--n", str(args.n), "--dtype", args.dtype, "--cycle", args.cycle,
+           "--trace-child", "--full", "--n", str(args.n), "--dtype", args.dtype, "--cycle", args.cycle,
            "--steps", str(args.steps), "--warmup", str(args.warmup), "--ops", args.ops]
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=330)
@@ -548,7 +608,7 @@ def live_pmc(args):
         d = tempfile.mkdtemp(prefix="pgmg_pmc_")
         cmd = ["timeout", "-s", "KILL", "150", prof, "--pmc", ctr, "--output-format", "csv",
                "-d", d, "-o", "run", "--", sys.executable, str(ROOT / "bench.py"), "--pmc-child",
-               "--n", str(args.n), "--dtype", args.dtype, "--cycle", args.cycle,
+               "--full", "--n", str(args.n), "--dtype", args.dtype, "--cycle", args.cycle,
                "--general-rhs", args.general_rhs, "--fast-mode", args.fast_mode, "--ops", args.ops]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=180)
@@ -769,11 +829,13 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         return float(tt.item())
 
-    want = golden_hash(args.cycle, args.n, args.warmup + args.steps) if args.dtype == "f64" else None
+    # --full: phi's hash after every repetition against the reference's (a plain run checks none)
+    want = (golden_hash(args.cycle, args.n, args.warmup + args.steps)
+            if args.full and args.dtype == "f64" else None)
     # the latency floor of the strips' collectives on this device (world-1 RCCL communicator,
     # rank 0 only): what DESIGN §5 prices a dependent exchange group at
     rccl_floor = None
-    if rank == 0 and not (solo or host_tp):
+    if args.full and rank == 0 and not (solo or host_tp):
         try:
             rccl_floor = dict(pg.rccl_latency(device, 200), what=(
                 "world-1 RCCL communicator on this GPU, hipEvents over 200 calls: a grouped "
@@ -810,22 +872,31 @@ def main():
         return out
 
     def run_leg(extra_flags, reps, n=None, warm=None, steps=None, want_hash=None,
-                inst_reps=INST_REPS):
+                inst_reps=INST_REPS, dump="", prime=0):
         """`reps` clean repetitions on one context (set_problem restarts each from phi0 = 0)
         + inst_reps repetitions with per-pass events on a second (per pass, the median over
         them; on row strips also events around every collective group: per-rank compute vs
-        RCCL time); returns times, parity, passes"""
+        RCCL time; 0: no second context, no per-pass figures); returns times, parity, passes.
+        dump: a directory for the clean context's result after its last timed call; prime:
+        untimed cycles on the clean context before its first repetition"""
         warm = max(args.warmup, 0) if warm is None else warm
         steps = args.steps if steps is None else steps
         want_hash = want if want_hash is None else want_hash
         out = {"times": [], "parity": [], "passes": [], "inst_dt": None, "split": []}
         inst_dt, inst_passes = [], []
-        for inst in (False, True):
+        for inst in ((False, True) if inst_reps > 0 else (False,)):
             fl = extra_flags
             if inst:
                 fl |= pg.PGMG_FLAG_TIME_FINE | (pg.PGMG_FLAG_TIME_COMM if world > 1 else 0)
             s = new_solver(fl, n=n)
             run = {"V": s.vcycle, "W": s.wcycle, "F": s.fcycle}[args.cycle]
+            if prime > 0 and not inst:
+                # part of setting up: the context's first cycles (first touch of its grids, the
+                # clocks of an idle GPU) run before the one repetition, as they do before the
+                # median repetition of --full's five
+                s.set_problem()
+                run(prime)
+                s.sync()
             for _ in range(inst_reps if inst else reps):
                 s.set_problem()
                 run(warm)
@@ -857,8 +928,9 @@ def main():
                     out["enq"] = t_enq - t0
                     out["dev_ms"] = s.last_elapsed_ms()
                     if not solo:
-                        h = s.solution_hash(0)
-                        out["parity"].append(None if want_hash is None or h is None else h == want_hash)
+                        # (collective on row strips: every rank holds the same want_hash)
+                        h = s.solution_hash(0) if want_hash is not None else None
+                        out["parity"].append(None if h is None else h == want_hash)
                     out["spec"] = (s.dist_info(), s.spec_levels())
                     out["carry"] = s.carry_info()
             out["vbytes"] = s.vcycle_bytes()
@@ -867,7 +939,11 @@ def main():
             out["gen"] = s.fused and s.fine_pass_bytes(3) < s.fine_pass_bytes(0)
             out["r2"] = world > 1 and not s.dist_info()[0]
             out["comm_ranks"] = s.comm_ranks()
+            if dump and not inst and not solo:
+                dump_outputs(s, dump, rank, world)
             s.close()
+        if not inst_dt:
+            return out
         out["inst_dt"] = statistics.median(inst_dt)
         out["passes"] = [(w, inst_passes[0][i][0], statistics.median(r[i][1] for r in inst_passes))
                          for i, w in enumerate(PASSES)]
@@ -881,7 +957,9 @@ def main():
             out["rank_split"] = rank_split_summary(gather(mine), out["inst_dt"], steps)
         return out
 
-    main_leg = run_leg(0, max(1, args.reps))
+    main_leg = run_leg(0, max(1, args.reps), inst_reps=INST_REPS if args.full else 0,
+                       dump=args.dump_outputs,
+                       prime=0 if args.full else max(args.warmup, 0) + min(args.steps, PRIME_STEPS))
     # BASELINE configs[3]'s grid (N = 32769) on the same N ranks: SURVEY §8(e) asks for
     # V-cycles/s at 1, 2, 4 and 8 GPUs at 16385 AND 32769; the N = 1 number is other_configs'
     # "configs[3]'s grid on ONE MI355X" (1 + 5 cycles, median of 3, the same shape)
@@ -1096,6 +1174,10 @@ def main():
             "scaling": "strong",
             "vs_baseline": None,
             "dtype": args.dtype,
+            # false: a plain run (the headline figure alone: parity, roofline and every leg
+            # below null or absent); true: the whole study
+            "full": args.full,
+            "outputs": args.dump_outputs or None,
             "data": "synthetic: the reference's own problem, phi0=0, f=2*pi^2*sin(pi x)sin(pi y)",
             "config": {
                 "workload": f"{args.cycle}-cycle N={n} ({n - 1}^2 cells), 2+2 Jacobi (v1=v2=1), "
@@ -1121,7 +1203,8 @@ def main():
                               "fixture": "tests/golden/cycles.json"},
             "roofline": roof[0] if roof else None,
             "roofline_other": roof[1:],
-            "instrumented_ms_per_step": round(main_leg["inst_dt"] * 1e3 / args.steps, 4),
+            "instrumented_ms_per_step": (round(main_leg["inst_dt"] * 1e3 / args.steps, 4)
+                                         if main_leg["inst_dt"] is not None else None),
             "vcycle_algorithmic_gbps": round(main_leg["vbytes"] / med * args.steps / 1e9, 2),
             "vcycle_device_ms": round(main_leg["dev_ms"] / args.steps, 4),
             "host_enqueue_ms_per_step": round(main_leg["enq"] * 1e3 / args.steps, 4),

@@ -18,7 +18,7 @@ def main():
         for combo in combos:
             env = dict(os.environ)
             env.update(dict(combo))
-            out = subprocess.run([sys.executable, "bench.py", "--steps", "20", "--warmup", "3",
+            out = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "20", "--warmup", "3",
                                   "--cpu-baseline", "off"], env=env, capture_output=True,
                                  text=True, timeout=300)
             line = next((l for l in out.stdout.splitlines() if l.startswith("{")), None)

@@ -25,7 +25,7 @@ for s in $STEPS; do
     strips) run strips 400 python -m pytest tests/test_gpu_strips.py -m gpu -q -rf -x ;;
     fcycle) run fcycle 600 python -m pytest tests/test_gpu_fcycle.py -m gpu -q -rf ;;
     tests-fast) run tests 600 python -u -m pytest tests -m "gpu and not slow" -v -rf --timeout 200 --timeout-method thread ;;
-    bench) run bench 600 python bench.py --steps 20 --warmup 3 ;;
+    bench) run bench 600 python bench.py --full --steps 20 --warmup 3 ;;
     fp32) run fp32 600 python -m pytest tests/test_gpu_fp32.py -m gpu -q -rf ;;
     bench32) run bench32 600 python bench.py --steps 20 --warmup 3 --dtype f32 --cpu-baseline off ;;
     sweep) run sweep 900 python scripts/fp32_sweep.py --out gpurun_out/fp32_sweep.json ;;

@@ -28,13 +28,13 @@ for s in ${STEPS}; do
     carry) step carry 600 python -u -m pytest tests/test_gpu_carry.py -x -v --timeout 300 --timeout-method thread ;;
     smoke) step smoke 120 python -c "import __graft_entry__ as g; g.smoke()" ;;
     tests) step tests 900 python -u -m pytest tests/ -m gpu -q --timeout 300 --timeout-method thread ;;
-    bench) step bench 600 python bench.py --gpus 1 --warmup 5 --steps 20 --save-profiles ${OUT}/prof ;;
+    bench) step bench 600 python bench.py --full --gpus 1 --warmup 5 --steps 20 --save-profiles ${OUT}/prof ;;
     bench_F) step bench_F 300 python bench.py --cycle F --warmup 2 --steps 20 --cpu-baseline off --pmc off --trace off ;;
     bench_W) step bench_W 300 python bench.py --cycle W --n 4097 --warmup 2 --steps 10 --cpu-baseline off --pmc off --trace off ;;
-    bench_f32) step bench_f32 400 python bench.py --dtype f32 --warmup 5 --steps 20 --cpu-baseline off --save-profiles ${OUT}/prof_f32 ;;
+    bench_f32) step bench_f32 400 python bench.py --full --dtype f32 --warmup 5 --steps 20 --cpu-baseline off --save-profiles ${OUT}/prof_f32 ;;
     solo2) step solo2 300 env PGMG_BENCH_SOLO=1 python bench.py --gpus 2 --warmup 2 --steps 10 --reps 2 ;;
     solo8) step solo8 400 env PGMG_BENCH_SOLO=1 python bench.py --gpus 8 --warmup 2 --steps 10 --reps 2 ;;
-    host2) step host2 400 env PGMG_BENCH_TRANSPORT=host python bench.py --gpus 2 --warmup 2 --steps 5 --reps 2 ;;
+    host2) step host2 400 env PGMG_BENCH_TRANSPORT=host python bench.py --full --gpus 2 --warmup 2 --steps 5 --reps 2 ;;
     stagger) step stagger 600 env PGMG_LIB=$PWD/parallel-geometric-multigrid-for-poisson-problem_amd/libpgmg_probe.so python scripts/stagger_probe.py --staggers ${STAGGERS:-0,4096,65536,1048576} ;;
     variants) step variants 600 env PGMG_LIB=$PWD/parallel-geometric-multigrid-for-poisson-problem_amd/libpgmg_probe.so python scripts/stagger_probe.py --reps 5 --variants "${VARIANTS}" ;;
     ctrace) step ctrace 300 rocprofv3 --kernel-trace --output-format csv -d ${OUT}/ctrace -o run -- python3 scripts/carry_trace.py && step ctrace_an 60 python3 scripts/carry_trace.py --analyse ${OUT}/ctrace ;;

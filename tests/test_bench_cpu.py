@@ -59,8 +59,58 @@ def test_bench_options_listed():
                        timeout=120, env=_env())
     assert r.returncode == 0, r.stderr[-2000:]
     for opt in ("--gpus", "--steps", "--warmup", "--big-grid", "--other-configs", "--cycle",
-                "--save-profiles", "--trace", "--pmc", "--cpu-baseline", "--ops"):
+                "--save-profiles", "--trace", "--pmc", "--cpu-baseline", "--ops", "--full",
+                "--dump-outputs"):
         assert opt in r.stdout, opt
+
+
+def test_plain_run_turns_every_leg_off(monkeypatch):
+    """Without --full none of the study's legs runs and one repetition is timed; with it each
+    leg follows its own option and five are."""
+    bench = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and a.reps == 1 and a.steps == 7 and a.dump_outputs == ""
+    assert all(getattr(a, leg) == "off" for leg in bench.FULL_LEGS)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--pmc", "off", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.reps == 5 and a.pmc == "off" and a.dump_outputs == "d"
+    assert all(getattr(a, leg) == "auto" for leg in bench.FULL_LEGS if leg != "pmc")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--reps", "3"])
+    assert bench.parse().reps == 3
+
+
+def test_dump_outputs_files(tmp_path):
+    """--dump-outputs: a small phi whole, a large one as the same seeded sample every time
+    (float64, within the size limit), and the sweep counts."""
+    import numpy as np
+    bench = _bench()
+
+    class S:
+        def __init__(self, n):
+            self.phi = np.arange(n * n, dtype=np.float64).reshape(n, n)
+
+        def solution(self):
+            return self.phi
+
+        def stats(self):
+            return 123, 4
+
+    bench.dump_outputs(S(33), tmp_path / "a")
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["phi.npy", "stats.npy"]
+    got = np.load(tmp_path / "a" / "phi.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, np.arange(33 * 33, dtype=np.float64))
+    assert np.load(tmp_path / "a" / "stats.npy").tolist() == [123.0, 4.0]
+    n = 2600   # 54 MB of float64: above the limit
+    assert n * n * 8 > bench.DUMP_MAX_BYTES
+    big = S(n)
+    bench.dump_outputs(big, tmp_path / "b")
+    bench.dump_outputs(big, tmp_path / "c")
+    b, c = np.load(tmp_path / "b" / "phi_sample.npy"), np.load(tmp_path / "c" / "phi_sample.npy")
+    assert b.dtype == np.float64 and b.nbytes == bench.DUMP_MAX_BYTES and np.array_equal(b, c)
+    # the stub's phi holds its own flat index: sorted indices inside the grid, spread over it
+    assert np.all(np.diff(b) >= 0) and b[0] >= 0 and b[-1] < n * n and b[-1] - b[0] > 0.99 * n * n
+    assert not (tmp_path / "b" / "phi.npy").exists()
 
 
 def test_op_cases_build_and_match_kernel_names():
