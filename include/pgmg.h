@@ -137,7 +137,7 @@ extern "C" {
                                         pass runs ~3-4 % faster in a process's first context) */
 #define PGMG_FLAG_NO_SPIN 1048576u /* one GPU: a speculative call waits for its validation with a
                                       blocking stream wait instead of polling the reply word in
-                                      pinned memory (pgmg_ctx.hip reply_wait) */
+                                      pinned memory (pgmg_spec.hip reply_wait) */
 #define PGMG_FLAG_HOST_TRANSPORT 2048u /* world > 1 without RCCL: nccl_unique_id points to
                                        a pgmg_host_transport; every message and reduction
                                        is staged through host memory and handed to the

@@ -1,5 +1,5 @@
-// pgmg_ctx.h — the context object behind the C ABI (shared by the orchestration
-// in pgmg_ctx.hip and the row-strip communication layer in pgmg_comm.hip).
+// pgmg_ctx.h — the context object behind the C ABI (shared by the orchestration's files,
+// mapped in pgmg_ctx.hip's header, and the row-strip communication layer in pgmg_comm.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -56,6 +56,74 @@ struct HaloReq {
     int depth;
 };
 
+// Three lifetimes: pgmg_ctx itself holds what lives as long as the context or is a result
+// read after a call; SpecHistory what the speculation learned about the current problem
+// (reset by a new problem and by pgmg_set_eps: its predictions are relative to eps);
+// CallState what means something only while one call is being enqueued.
+struct SpecHistory {
+    bool spec_off = false;        // switched off: a finest-level check fires
+    bool fspec_off = false;       // a speculative F call was rolled back: in-stream (problem)
+    std::vector<char> lvl_exact;  // per bulk level: its checks fire (soon): decide in-stream
+    std::vector<char> lvl_fire;   // per bulk level: its checks keep firing: predicted to fire
+    std::vector<char> lvl_fire_block;   // a "fires" prediction failed: never again (this problem)
+    std::vector<int> lvl_kx;      // per bulk level: its first cycles of the segment recorded
+                                  // "does not fire" (then in-stream); lvl_vis counts its visits
+    std::vector<int> lvl_vis;
+    std::vector<double> lvl_fire_try;   // norm at the last segment split made for the level to
+                                        // become "fires" (0: none; no second split before it halves)
+    std::vector<std::vector<double>> lvl_hist;   // per bulk level: its last check norms
+    // W-cycle plan (pgmg_cycle.hip "W-cycle plans"): per visit of a bulk level in the cycle, the
+    // largest and smallest check norm of that visit in the last validated cycle
+    std::vector<double> wmax, wmin, wrho;   // wrho: the visit's decay over the last two cycles
+    int wplan_gamma = 0;          // gamma of the plan (0: none)
+    int wplan_seg = 0;            // cycles of the segment the plan was taken from
+    bool wplan_off = false;       // a plan's prediction failed: none for this problem
+
+    void reset(int nb)   // speculate again, every one of the nb bulk levels
+    {
+        *this = SpecHistory{};
+        lvl_exact.assign(nb + 1, 0);
+        lvl_fire.assign(nb + 1, 0);
+        lvl_fire_block.assign(nb + 1, 0);
+        lvl_fire_try.assign(nb + 1, 0.0);
+        lvl_kx.assign(nb + 1, 0);
+        lvl_vis.assign(nb + 1, 0);
+        lvl_hist.assign(nb + 1, std::vector<double>());
+    }
+};
+
+// What a cycle call's outer layers hand to the kernel sequences below them.  run_cycles and
+// pgmg_fcycle restore CallState{} on every exit path (CallScope, pgmg_host.h), errors included.
+struct CallState {
+    // a device-bound call in place: the first k_pre reads x_in, the last k_post writes x_out
+    // (pitch ext_P) instead of the level-0 grids; defer_post stops before that last k_post
+    // (a speculative call validates its checks first: x_out is also x_in), pend_pr is the
+    // pre-smoothed iterate it will read
+    const void *x_in = nullptr;
+    void *x_out = nullptr;
+    long long ext_P = 0;
+    bool defer_post = false;
+    void *pend_pr = nullptr;
+    bool lean = false;            // the cycles being enqueued record their checks
+    bool fspec = false;           // the F-cycles being enqueued are speculative
+    int spec_gamma = 1;           // gamma of the speculative call being enqueued
+    // the carry (pgmg_cycle.hip "carry")
+    bool carry_use = false;       // the segment being enqueued starts from the carry
+    bool carry_make = false;      // the segment being enqueued ends with the carry pass
+    bool carry_made = false;      // ... and it did
+    bool carry_took = false;      // the last segment enqueued started from the carry
+    int carry_chk = -1;           // index in chks of the carried pre-smooth's check
+    int wvisit = 0, wseg = 0;     // W visits enqueued in this segment; its cycles
+    int cur_visit = -1;           // the visit whose checks chk_log records (-1: none)
+    // speculative F-cycle followed by another in the call: its finest k_post also formed level
+    // 2's restriction (k_post_r2), which the next F-cycle of the call starts from
+    bool fr2_made = false;
+    // F-cycle climb: the level whose V-cycle and smooth(3) are being enqueued regenerates its
+    // analytic f in-kernel from these tables (0: none)
+    int gen_level = 0;
+    const double *lgfx = nullptr, *lgsy = nullptr;
+};
+
 }  // namespace pgmg
 
 struct pgmg_ctx {
@@ -104,33 +172,15 @@ struct pgmg_ctx {
     // pgmg_fcycle), nullptr when level-0 f must be streamed
     const double *rgfx = nullptr, *rgsy = nullptr;
     double *fmg_gtab = nullptr;   // fx/sy tables of the F-cycle's level-0 RHS
-    // speculative calls (pgmg_ctx.hip "speculative calls"): the early-exit checks of a
+    // speculative calls (pgmg_spec.hip "speculative calls"): the early-exit checks of a
     // call are recorded instead of decided in-stream, validated once after the call
     bool spec = false;            // enabled for this context (fused cycle, no EXACT flag)
-    bool spec_off = false;        // switched off: a finest-level check fires
-    std::vector<char> lvl_exact;  // per bulk level: its checks fire (soon): decide in-stream
-    std::vector<char> lvl_fire;   // per bulk level: its checks keep firing: predicted to fire
-    std::vector<char> lvl_fire_block;   // a "fires" prediction failed: never again (this problem)
-    std::vector<int> lvl_kx;      // per bulk level: its first cycles of the segment recorded
-                                  // "does not fire" (then in-stream); lvl_vis counts its visits
-    std::vector<int> lvl_vis;
-    std::vector<double> lvl_fire_try;   // norm at the last segment split made for the level to
-                                        // become "fires" (0: none; no second split before it halves)
-    std::vector<std::vector<double>> lvl_hist;   // per bulk level: its last check norms
+    pgmg::SpecHistory hist;            // what the speculation learned about the current problem
+    pgmg::CallState call;           // set only while a call is being enqueued
     double *chk_norm = nullptr;   // per-check norms of the last validation
     unsigned *mark_dev = nullptr; // row strips: per-level marks agreed by allreduce
     std::vector<double> hnorm;
     std::vector<unsigned> hflag;
-    bool lean = false;            // the cycles being enqueued record their checks
-    int spec_gamma = 1;           // gamma of the speculative call being enqueued
-    // W-cycle plan (pgmg_ctx.hip "W-cycle plans"): per visit of a bulk level in the cycle, the
-    // largest and smallest check norm of that visit in the last validated cycle
-    std::vector<double> wmax, wmin, wrho;   // wrho: the visit's decay over the last two cycles
-    int wplan_gamma = 0;          // gamma of the plan (0: none)
-    int wplan_seg = 0;            // cycles of the segment the plan was taken from
-    bool wplan_off = false;       // a plan's prediction failed: none for this problem
-    int wvisit = 0, wseg = 0;     // visits enqueued in this segment; its cycles
-    int cur_visit = -1;           // the visit whose checks chk_log records (-1: none)
     long long wcount[3] = {0, 0, 0};   // the last W call's visits per mode
     std::vector<int> chk_visit;   // per recorded check: its visit (-1: level 0)
     double *plog = nullptr;       // partials of every recorded check of the current call
@@ -143,15 +193,10 @@ struct pgmg_ctx {
     long long chk_cap = 0;
     unsigned pin_seq = 0;         // the last validation reply's sequence word
     pgmg::Grid bk;                // level-0 solution at the start of the call (rollback)
-    // speculative F-cycles (pgmg_ctx.hip "speculative F-cycles"): every bulk check of the
+    // speculative F-cycles (pgmg_fcycle.hip "speculative F-cycles"): every bulk check of the
     // climb recorded "does not fire"; a rollback restarts the call's first climb from the
     // tail top's restricted grid, saved here (the only input of the climb)
-    bool fspec = false;           // the F-cycles being enqueued are speculative
-    bool fspec_off = false;       // a speculative F call was rolled back: in-stream (problem)
     pgmg::Grid ftop;
-    // speculative F-cycle followed by another in the call: its finest k_post also forms level
-    // 2's restriction (k_post_r2; fr2_want while it is enqueued, fr2_made once it was)
-    bool fr2_want = false, fr2_made = false;
     unsigned long long *stats_bk = nullptr;
     long long rollbacks = 0;
     unsigned *ppflags = nullptr;  // k_postpre_decide flags
@@ -160,12 +205,8 @@ struct pgmg_ctx {
     // tables of every level (built on the first call)
     pgmg::Grid Ffmg;
     // F-cycle climb: regenerated-RHS tables (factor*sx, sy) of every bulk level of the FMG
-    // chain (level l at fmg_gtab + fmg_goff[l]); the level whose V-cycle and smooth(3) are
-    // being enqueued regenerates its analytic f in-kernel (gen_level, lgfx, lgsy)
+    // chain (level l at fmg_gtab + fmg_goff[l]; CallState::gen_level names the one in use)
     std::vector<size_t> fmg_goff;
-    int gen_level = 0;
-    const double *lgfx = nullptr, *lgsy = nullptr;
-    int fmg_f_swapped = -1;   // bulk level whose L.F is traded with Ffmg_l (climb), or -1
     std::vector<pgmg::Grid> Ffmg_l;   // the analytic RHS of bulk levels 1.. of the FMG climb
     bool fmg_rhs_ready = false;   // Ffmg holds the level-0 analytic RHS of the FMG h chain
     double *fmg_tab = nullptr;
@@ -175,32 +216,18 @@ struct pgmg_ctx {
     double *ext_phi = nullptr;
     const double *ext_f = nullptr;   // nullptr: the analytic RHS (regenerated in-kernel)
     bool ext_inplace = false;        // the finest passes read / write ext_phi in place
-    // while a call is enqueued: the first k_pre reads x_in, the last k_post writes x_out
-    // (pitch ext_P) instead of the level-0 grids; defer_post stops before that last k_post
-    // (a speculative call validates its checks first: x_out is also x_in), pend_pr is the
-    // pre-smoothed iterate it will read
-    const void *x_in = nullptr;
-    void *x_out = nullptr;
-    long long ext_P = 0;
-    bool defer_post = false;
-    void *pend_pr = nullptr;
-    // the carry (pgmg_ctx.hip "carry"): a speculative V call on the context's own grids ends
+    // the carry (pgmg_cycle.hip "carry"): a speculative V call on the context's own grids ends
     // with the carry pass, which stores its result and the next cycle's restriction into
     // lv[1].F; the next V call starts from them (its first finest pass recomputes the
     // pre-smooth) when no entry touched the problem in between
     bool carry = false;           // lv[1].F holds the validated restriction of lv[0].A's pre-smooth
-    bool carry_use = false;       // the segment being enqueued starts from the carry
-    bool carry_make = false;      // the segment being enqueued ends with the carry pass
-    bool carry_made = false;      // ... and it did
-    bool carry_took = false;      // the last segment enqueued started from the carry
-    int carry_chk = -1;           // index in chks of the carried pre-smooth's check
     long long carry_n[3] = {0, 0, 0};   // calls that took a carry, carries made, dropped
 };
 
 namespace pgmg {
 
 // stagger: the origin shifted by this many bytes (a multiple of 128) past the usual one;
-// shuffle: a grid of 256 MB or more is built from shuffled physical chunks (pgmg_ctx.hip)
+// shuffle: a grid of 256 MB or more is built from shuffled physical chunks (pgmg_mem.hip)
 int alloc_grid(Grid &g, const Level &L, size_t stagger = 0, bool shuffle = false);
 void free_grid(Grid &g);
 // dispatch on the context's element type

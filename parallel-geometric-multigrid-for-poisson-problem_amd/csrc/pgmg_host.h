@@ -1,0 +1,118 @@
+// pgmg_host.h — shared by the orchestration's files (mapped in pgmg_ctx.hip's header): error
+// macros, the functions that cross a file boundary, two argument-block builders.  Host only.
+#pragma once
+#include "pgmg_ctx.h"
+#include "pgmg_fused.h"
+
+#define PGMG_TRY(expr)            \
+    do {                          \
+        const int e_ = (expr);    \
+        if (e_) return e_;        \
+    } while (0)
+#define HIPC(expr) PGMG_HIPC(expr)
+
+namespace pgmg {
+
+// Wait for the context's stream.  On row strips through the transport's wait, which polls
+// RCCL's asynchronous error state and gives up after cfg.comm_timeout_s instead of hanging
+// on a dead or stuck peer.
+inline int stream_wait(pgmg_ctx *c)
+{
+    if (c->comm) return c->comm->wait(c->s);
+    PGMG_HIPC(hipStreamSynchronize(c->s));
+    return PGMG_OK;
+}
+
+// held by run_cycles and pgmg_fcycle: c->call is clear again on every exit path
+struct CallScope {
+    pgmg_ctx *c;
+    ~CallScope() { c->call = CallState{}; }
+};
+
+// --- pgmg_mem.hip
+bool registered_span(intptr_t lo, intptr_t hi);   // is [lo, hi) inside ONE registered allocation?
+bool is_device_ptr(const void *p);
+// p lies in a shuffled (virtual-memory-mapped) grid: the runtime's 2D copies and memsets refuse
+// those ranges, so every grid transfer checks and takes a kernel or a 1D copy instead
+bool is_vmm(const void *p);
+
+// --- pgmg_cycle.hip
+// k_post row range of a fused level: the strip, or on distributed levels below the finest
+// the strip plus kPostExt rows past each edge (see enqueue_fused_level)
+struct PostRows {
+    int jc0, jc1, row_lo, row_hi;
+};
+PostRows post_rows(const pgmg_ctx *c, int l);
+// partial sums a tile pass of bulk level l writes on this rank (0: no tile pass there);
+// pre: the rank's coarse rows, post: its k_post rows (post_rows)
+int tile_np(const pgmg_ctx *c, int l, bool post);
+struct StripRows {
+    int jc0, jc1;         // coarse-row segments [jc0, jc1)
+    int row_lo, row_hi;   // fine rows this rank writes
+    int rc_lo, rc_hi;     // coarse rows this rank restricts into
+    int x_lo, x_hi;       // rows of the rare-path scratch S (row_lo - 4 .. row_hi + 4)
+};
+StripRows strip_rows(const Level &L, const Level &C);
+// A log slice for one check of mode `mode` (nullptr outside speculative calls; an in-stream
+// check is logged -- its norm only, for the per-level policy -- on one GPU)
+double *chk_log(pgmg_ctx *c, int np, int level, int mode);
+// dispatchers on the element type (enqueue_cycle, enqueue_tail: pgmg_ctx.h)
+int enqueue_smooth(pgmg_ctx *c, int l, int which, int v, bool x0_zero);
+// pin: F-cycle climb; fr2_want: the finest k_post also forms level 2's restriction (k_post_r2)
+int enqueue_fused_level(pgmg_ctx *c, int l, int gamma, bool x0_zero, bool pin, bool fr2_want);
+int enqueue_last_post(pgmg_ctx *c);
+int run_cycles_plain(pgmg_ctx *c, int ncycles, int gamma, bool rec0 = true);
+
+// --- pgmg_spec.hip
+// log doubles and checks of one visit of level l >= 1 (the tail decides in-kernel)
+void spec_need_level(pgmg_ctx *c, int l, int gamma, long long *dbl, long long *nchk);
+int spec_reserve(pgmg_ctx *c, long long dbl, long long nchk);
+int spec_validate(pgmg_ctx *c, unsigned *h_out, bool *overflow_out, int n_any);
+int run_cycles_spec(pgmg_ctx *c, int ncycles, int gamma);
+
+// --- pgmg_ctx.hip
+void sine_tables(const pgmg_config &cfg, int N, double h, std::vector<double> &sx,
+                 std::vector<double> &sy, double &factor);
+int ext_stage_in(pgmg_ctx *c, bool inplace);
+int ext_stage_out(pgmg_ctx *c);
+
+// the tail launch's arguments every caller shares (visits, x0_from_global, fmg_*: the caller's)
+template <class T>
+inline TailArgsT<T> tail_args(const pgmg_ctx *c)
+{
+    const Level &Lt = c->lv[c->nb];
+    TailArgsT<T> t{};
+    t.f_top = G<T>(Lt.F);
+    t.e_top = G<T>(Lt.A);
+    t.P_top = Lt.P;
+    t.N_top = Lt.N;
+    t.h_top = Lt.h;
+    t.v1 = c->cfg.v1;
+    t.v2 = c->cfg.v2;
+    t.coarse_iter = c->cfg.coarse_iter;
+    t.n_coarse = c->cfg.n_coarse;
+    t.eps = c->cfg.eps;
+    t.stats = c->stats;
+    return t;
+}
+
+// level geometry of a k_postpre-shaped pass (k_postpre, fused smooth(3)) on level L above C
+template <class T>
+inline void postpre_geometry(PostPreArgsT<T> &q, const Level &L, const Level &C)
+{
+    const StripRows sr = strip_rows(L, C);
+    q.hh = (T)L.hh;
+    q.ih = (T)L.ih;
+    q.N = L.N;
+    q.P = L.P;
+    q.Nc = C.N;
+    q.Pc = C.P;
+    q.jc0 = sr.jc0;
+    q.jc1 = sr.jc1;
+    q.row_lo = sr.row_lo;
+    q.row_hi = sr.row_hi;
+    q.rc_lo = sr.rc_lo;
+    q.rc_hi = sr.rc_hi;
+}
+
+}  // namespace pgmg

@@ -10,8 +10,9 @@ B=$PKG/build_v_$NAME
 mkdir -p $B
 HIPFLAGS="-O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fPIC -Wall -Wno-unused-result -I$PKG/../include -DPGMG_TUNING $FLAGS"
 pids=()
-for s in pgmg_fused pgmg_coarse pgmg_kernels pgmg_tail pgmg_gops pgmg_ctx pgmg_ops pgmg_comm; do
-  /opt/rocm/bin/hipcc $HIPFLAGS -c $PKG/csrc/$s.hip -o $B/$s.o &
+# the translation units: the Makefile's SRCS line
+for s in $(sed -n 's/^SRCS = //p' $PKG/Makefile); do
+  /opt/rocm/bin/hipcc $HIPFLAGS -c $PKG/csrc/$s -o $B/${s%.hip}.o &
   pids+=($!)
 done
 for p in "${pids[@]}"; do wait $p; done

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Same-box A/B of the carry (pgmg_ctx.hip "carry"): the headline call shape (a fresh problem,
+"""Same-box A/B of the carry (pgmg_cycle.hip "carry"): the headline call shape (a fresh problem,
 a W-cycle warmup call, then a K-cycle call, timed) and one-cycle calls, with and without
 PGMG_FLAG_NO_CARRY, interleaved over R rounds.  One JSON line per (round, variant, shape).
 

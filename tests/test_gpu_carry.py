@@ -1,4 +1,4 @@
-"""GPU: the carry (r06, include/pgmg.h above pgmg_vcycle; pgmg_ctx.hip "carry").
+"""GPU: the carry (r06, include/pgmg.h above pgmg_vcycle; pgmg_cycle.hip "carry").
 
 A speculative V call on the context's own grids ends with the carry pass, which also runs the
 next cycle's pre-smooth, residual and restriction; the next pgmg_vcycle on the same problem
@@ -201,7 +201,7 @@ def test_carry_full_size_single_calls(pgmg, golden_cycles):
 
 
 def test_spin_wait_gives_the_same_words(pgmg, golden_cycles):
-    """The validation's wait polls the reply word in pinned memory (pgmg_ctx.hip reply_wait);
+    """The validation's wait polls the reply word in pinned memory (pgmg_spec.hip reply_wait);
     PGMG_FLAG_NO_SPIN waits on the stream instead: the same phi, statistics and carries over
     one-cycle calls at 4097, and the reference's hash after 12 cycles."""
     gold = _golden(golden_cycles, 4097)

@@ -1,4 +1,4 @@
-"""GPU: speculative F-cycles (pgmg_ctx.hip "speculative F-cycles") against the same F-cycles
+"""GPU: speculative F-cycles (pgmg_fcycle.hip "speculative F-cycles") against the same F-cycles
 decided in-stream (PGMG_FLAG_EXACT_DIST) and the oracle.
 
 A call of F-cycles records every bulk early-exit check of its climb -- the V-cycles' passes and

@@ -1,5 +1,5 @@
 """GPU: grids of 256 MB and more built from shuffled physical chunks (HIP virtual memory;
-pgmg_ctx.hip "Shuffled physical placement", the one-GPU default since r06) hold and move the
+pgmg_mem.hip "Shuffled physical placement", the one-GPU default since r06) hold and move the
 same words as plain hipMalloc grids (PGMG_FLAG_NO_SHUFFLE): host uploads of phi and f, the
 runtime's 2D copies avoided on them (set_problem, get_solution, the staged device-array path),
 V-cycles, the residual norm and the carry -- at N = 8193 (537 MB level-0 grids)."""

@@ -1,4 +1,4 @@
-"""Speculative calls on converged coarse levels (pgmg_ctx.hip "predicted to fire", "segment
+"""Speculative calls on converged coarse levels (pgmg_spec.hip "predicted to fire", "segment
 planning"), against the same solver with every check decided in-stream (PGMG_FLAG_EXACT_DIST).
 
 On the reference problem the bulk levels above the tail reach eps after ~27 V-cycles and from
@@ -55,7 +55,7 @@ def test_fire_prediction_bitwise(pgmg, oracle_mod, golden_cycles, N, calls):
 def test_fire_prediction_w_f_bitwise(pgmg, kind, N, calls):
     """W- and F-cycles: the second and third gamma visits of a level start from the previous
     visit's iterate, not from 0; their predicted-to-fire passes read x0 and store x1 (k_pre1 /
-    k_post1 without RECOMP).  W calls speculate on one GPU at every N (pgmg_ctx.hip "W-cycle
+    k_post1 without RECOMP).  W calls speculate on one GPU at every N (pgmg_cycle.hip "W-cycle
     plans": each visit of a bulk level planned from the same visit of the previous cycle);
     F-cycles run in-stream."""
     phi, det, info, masks = _calls(pgmg, N, calls, kind=kind)
@@ -113,3 +113,41 @@ def test_failed_fire_prediction_rolls_back(pgmg, oracle_mod):
     assert ia[1] >= 1, ia
     assert_bitwise(a, b, "after the rollback")
     assert da == db
+
+
+def test_history_reset_by_set_eps_and_set_problem(pgmg):
+    """The speculation history has one reset, shared by pgmg_set_eps and a new problem: after
+    either, no level is marked (in-stream or predicted to fire), the rollback count stands, and
+    the solver goes on exactly as one that never had the history.  N = 2049, 3 + 40 V-cycles:
+    the smallest shape here whose coarse levels get marked (smaller grids are not cross-fused
+    and do not speculate on V-cycles, so their spec_levels() bit 0 is constant)."""
+    N, calls = 2049, (3, 40)
+
+    def marks(s):
+        return s.spec_fire_levels() | s.spec_levels()
+
+    def three_more(s):
+        before = s.stats()
+        s.vcycle(3)
+        return s.solution_hash(), tuple(a - b for a, b in zip(s.stats(), before))
+
+    with pgmg.Solver(N) as s, pgmg.Solver(N, flags=pgmg.PGMG_FLAG_EXACT_DIST) as ref:
+        for x in (s, ref):
+            x.set_problem()
+            for n in calls:
+                x.vcycle(n)
+        assert marks(s) != 0, "no level marked: the resets below would pass vacuously"
+        rollbacks = s.dist_info()[1]
+        s.set_eps(s.cfg.eps)
+        assert (s.spec_levels(), s.spec_fire_levels()) == (0, 0)
+        assert s.dist_info()[1] == rollbacks
+        assert three_more(s) == three_more(ref)      # the in-stream solver from the same state
+
+        for n in calls:
+            s.vcycle(n)
+        assert marks(s) != 0
+        s.set_problem()
+        assert (s.spec_levels(), s.spec_fire_levels()) == (0, 0)
+        with pgmg.Solver(N) as fresh:
+            fresh.set_problem()
+            assert three_more(s) == three_more(fresh)
