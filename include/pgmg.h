@@ -254,7 +254,8 @@ int pgmg_pointer_is_device(const void *p, int *is_device);
  * context-owned buffer and checks it; the next pgmg_vcycle on the same problem starts from it
  * instead of running its own first pass (its first finest pass recomputes the pre-smooth from
  * phi in registers: no pass and no byte is added).  Entries that only read the problem (pgmg_get_solution, pgmg_solution_hash,
- * pgmg_residual_norm, pgmg_stats*, pgmg_sync ...) keep the carry; every entry that changes phi,
+ * pgmg_residual_norm, pgmg_monitor, pgmg_history, pgmg_stats*, pgmg_sync ...) keep the carry
+ * (pgmg_solve's checks between its one-cycle calls too); every entry that changes phi,
  * f, eps, the flags or the cycle kind (pgmg_set_problem*, pgmg_set_eps, pgmg_wcycle,
  * pgmg_fcycle, pgmg_bench_sweep, pgmg_phi_device -- its pointer allows writes -- ) drops it.
  * A carried pre-smooth whose early-exit check could fire is dropped, not rolled back.  Results
@@ -280,6 +281,81 @@ int pgmg_solution_hash(pgmg_ctx *ctx, int root, unsigned long long *hash);
 
 /* sqrt(sum over interior of r^2) for the current phi (synchronous). */
 int pgmg_residual_norm(pgmg_ctx *ctx, double *out);
+
+/* ---- Convergence monitor and solve-to-tolerance ----------------------------------------
+ * The counterpart of the reference driver's per-cycle history (MultigridTestRunner::run_cycle,
+ * 2_part_MG/MultiGridTestRunner.hpp:190-244: compute_residual + norm after each cycle, and with
+ * flag_err_norm_iteration ||phi - u|| / ||u||, :110-122 and :252-254).
+ *
+ * pgmg_monitor: one streaming pass over the current finest-level iterate, where it lies (the
+ * context's grid, or the caller's device arrays of pgmg_set_problem_device: nothing is staged or
+ * copied), gives up to three fp64 sums:
+ *   PGMG_MON_RESIDUAL  res_norm = sqrt(sum over interior points of r^2), r = f - ih (4x - x_l -
+ *                      x_r - x_u - x_d) in the expression order of DynamicGridUtils::
+ *                      compute_residual (DynamicGridUtils.hpp:59-69), evaluated in the context's
+ *                      element type, squared and summed in double;
+ *   PGMG_MON_ERROR     err_norm = sqrt(sum over ALL N*N points, boundary included, of e^2),
+ *                      e = (double)phi - u, u = sin(p pi x / a) sin(q pi y / a) from the host's
+ *                      sine tables (compute_function's product); exact_norm = sqrt(sum u^2);
+ *                      rel_error = err_norm / exact_norm.  Analytic problems only (f = NULL at
+ *                      pgmg_set_problem*): PGMG_ERR_STATE otherwise.
+ * Fields that were not asked for are NaN.  The sums are deterministic: per-workgroup partials in
+ * a fixed lane and row order, added in index order by a second launch (no floating-point
+ * atomics), the decomposition a function of N and the rank's rows only -- the same state gives
+ * the same bits, eager or graph, context-owned or device-bound.  Per-point terms are the
+ * reference's; only the summation order differs, so a norm agrees with the sequential sum within
+ * N^2 * 2^-52 relative.  Synchronous; collective on row strips (one halo exchange of phi, one
+ * rank-ordered allreduce of the three sums: every rank gets identical bits).
+ * pgmg_monitor, pgmg_monitor_time and pgmg_history only read the problem: they keep the carry. */
+#define PGMG_MON_RESIDUAL 1u
+#define PGMG_MON_ERROR    2u   /* analytic problems only (f = NULL at set_problem*) */
+typedef struct pgmg_monitor_out { double res_norm, err_norm, exact_norm, rel_error; } pgmg_monitor_out;
+int pgmg_monitor(pgmg_ctx *ctx, unsigned what, pgmg_monitor_out *out);
+/* Measurement: `reps` monitor passes (both launches each) back to back on the context's stream
+ * between two hipEvents, after two warm ones; mean device ms per pass, and the algorithmic HBM
+ * bytes of one pass (8 B per point of phi, + 8 B per interior point of a stored f; x elem/8). */
+int pgmg_monitor_time(pgmg_ctx *ctx, unsigned what, int reps, double *ms_per_pass, double *bytes);
+
+/* pgmg_solve: cycle until the residual norm meets a tolerance.  Check 0 happens before any
+ * cycle; at check i, after k_i cycles, with norm r_i, in this order:
+ *   1. r_i not finite                          -> PGMG_STOP_NONFINITE
+ *   2. r_i <= max(atol, rtol * r_0)            -> PGMG_STOP_CONVERGED
+ *   3. i >= 1 and stall_ratio > 0: r_i > stall_ratio * r_{i-1} extends a streak, anything else
+ *      resets it; a streak of stall_checks     -> PGMG_STOP_STALLED
+ *   4. k_i >= max_cycles                       -> PGMG_STOP_MAX_CYCLES
+ * otherwise min(check_every, max_cycles - k_i) more cycles run, one pgmg_vcycle / pgmg_wcycle /
+ * pgmg_fcycle call per chunk.  phi and pgmg_stats afterwards are bit for bit those of
+ * info.cycles plain cycles of that kind (the monitor adds no sweep and writes nothing a cycle
+ * reads); with check_every = 1 a V solve runs at the carried one-cycle-call rate.  Invalid
+ * options (negative counts, check_every < 1, stall_checks < 1, negative or non-finite
+ * tolerances, an unknown cycle or monitor bit) return PGMG_ERR_ARG before anything is enqueued;
+ * PGMG_MON_ERROR on a problem with a caller's f returns PGMG_ERR_STATE.  Collective on row
+ * strips: every rank sees the same norms and stops at the same check. */
+#define PGMG_CYCLE_V 0
+#define PGMG_CYCLE_W 1
+#define PGMG_CYCLE_F 2
+#define PGMG_STOP_CONVERGED 1
+#define PGMG_STOP_MAX_CYCLES 2
+#define PGMG_STOP_STALLED 3
+#define PGMG_STOP_NONFINITE 4
+typedef struct pgmg_solve_opts {
+    int cycle, max_cycles, check_every;
+    double rtol, atol;          /* target = max(atol, rtol * r0) */
+    double stall_ratio;         /* 0 = no stall test */
+    int stall_checks;
+    unsigned monitor;           /* PGMG_MON_RESIDUAL always on; | PGMG_MON_ERROR records rel_error too */
+} pgmg_solve_opts;
+typedef struct pgmg_solve_info {
+    int cycles, checks, reason;
+    double res0, res, rel_error /* NaN when not monitored */, elapsed_ms /* host wall time of the call */;
+} pgmg_solve_info;
+/* V, 30 cycles, a check every cycle, rtol 1e-3, atol 0, no stall test (stall_checks 2) */
+int pgmg_solve_opts_default(pgmg_solve_opts *o);
+int pgmg_solve(pgmg_ctx *ctx, const pgmg_solve_opts *o, pgmg_solve_info *info);
+/* The last pgmg_solve's checks, check 0 first: *n = their number; the first min(cap, *n) land
+ * in cycle[] (cycles run before the check), res[] and rel_error[] (NaN when not monitored); any
+ * of the arrays may be NULL. */
+int pgmg_history(pgmg_ctx *ctx, int cap, int *cycle, double *res, double *rel_error, int *n);
 
 /* Cumulative smoother sweeps and early exits since set_problem
  * (comparable with the oracle's counters). */

@@ -25,6 +25,9 @@ from ._capi import (PGMG_FLAG_LOOPBACK, PGMG_FLAG_NO_CROSS, PGMG_FLAG_NO_GRAPH,
                     PGMG_FLAG_NO_SPEC_FIRE, PGMG_FLAG_NO_CTILE, PGMG_FLAG_NO_CARRY, PGMG_FLAG_TIME_COMM, PGMG_FLAG_NO_SHUFFLE, PGMG_FLAG_NO_SPIN,
                     PGMG_PROLONG_REFERENCE,
                     PGMG_PROLONG_SYMMETRIC, PGMG_OK, PGMG_ERR_STATE, PgmgConfig, PgmgError,
+                    PGMG_MON_RESIDUAL, PGMG_MON_ERROR, PGMG_CYCLE_V, PGMG_CYCLE_W, PGMG_CYCLE_F,
+                    PGMG_STOP_CONVERGED, PGMG_STOP_MAX_CYCLES, PGMG_STOP_STALLED,
+                    PGMG_STOP_NONFINITE, PgmgMonitorOut, PgmgSolveOpts, PgmgSolveInfo,
                     check, load)
 
 PKG_DIR = pathlib.Path(__file__).resolve().parent
@@ -37,6 +40,9 @@ __all__ = [
     "PGMG_FLAG_STORED_RHS", "PGMG_FLAG_EXACT_DIST", "PGMG_FLAG_SOLO",
     "PGMG_FLAG_NO_RECOMPUTE", "PGMG_FLAG_NO_PIN", "PGMG_FLAG_NO_R2", "PGMG_FLAG_FAST", "PGMG_FLAG_NO_SPEC_FIRE", "PGMG_FLAG_NO_CTILE", "PGMG_FLAG_NO_CARRY", "PGMG_FLAG_TIME_COMM", "PGMG_FLAG_NO_SHUFFLE", "PGMG_FLAG_NO_SPIN",
     "PGMG_FLAG_HOST_TRANSPORT", "HostTransport", "DeviceGrid",
+    "PGMG_MON_RESIDUAL", "PGMG_MON_ERROR", "PGMG_CYCLE_V", "PGMG_CYCLE_W", "PGMG_CYCLE_F",
+    "PGMG_STOP_CONVERGED", "PGMG_STOP_MAX_CYCLES", "PGMG_STOP_STALLED", "PGMG_STOP_NONFINITE",
+    "PgmgSolveOpts", "PgmgSolveInfo", "PgmgMonitorOut",
 ]
 
 
@@ -253,6 +259,51 @@ class Solver:
         v = C.c_double()
         check(self.lib.pgmg_residual_norm(self.h, C.byref(v)), "pgmg_residual_norm")
         return v.value
+
+    def monitor(self, error=False, residual=True):
+        """One pass over the current iterate where it lies (pgmg_monitor): a PgmgMonitorOut
+        with res_norm and, with error=True (analytic problems), err_norm, exact_norm and
+        rel_error against the analytic solution; what was not asked for is NaN.  Keeps the
+        carry; collective on row strips."""
+        what = (PGMG_MON_RESIDUAL if residual else 0) | (PGMG_MON_ERROR if error else 0)
+        out = PgmgMonitorOut()
+        check(self.lib.pgmg_monitor(self.h, what, C.byref(out)), "pgmg_monitor")
+        return out
+
+    def monitor_time(self, reps=20, error=False, residual=True):
+        """(mean device ms, algorithmic bytes) of one monitor pass over `reps` back to back
+        (pgmg_monitor_time; measurement)."""
+        what = (PGMG_MON_RESIDUAL if residual else 0) | (PGMG_MON_ERROR if error else 0)
+        ms, b = C.c_double(), C.c_double()
+        check(self.lib.pgmg_monitor_time(self.h, what, int(reps), C.byref(ms), C.byref(b)),
+              "pgmg_monitor_time")
+        return ms.value, b.value
+
+    def solve(self, cycle="V", rtol=1e-3, atol=0.0, max_cycles=30, check_every=1,
+              stall_ratio=0.0, stall_checks=2, error=False):
+        """Cycle until the residual norm is at most max(atol, rtol * r0), the cycle cap, a
+        stall or a non-finite norm (pgmg_solve; the stop rule: include/pgmg.h).  Returns the
+        PgmgSolveInfo with a `.history` list of (cycle, res, rel_error), check 0 first."""
+        o = PgmgSolveOpts()
+        check(self.lib.pgmg_solve_opts_default(C.byref(o)), "pgmg_solve_opts_default")
+        kinds = {"V": PGMG_CYCLE_V, "W": PGMG_CYCLE_W, "F": PGMG_CYCLE_F}
+        o.cycle = kinds[cycle] if cycle in kinds else int(cycle)
+        o.rtol, o.atol, o.max_cycles, o.check_every = rtol, atol, int(max_cycles), int(check_every)
+        o.stall_ratio, o.stall_checks = stall_ratio, int(stall_checks)
+        o.monitor = PGMG_MON_RESIDUAL | (PGMG_MON_ERROR if error else 0)
+        info = PgmgSolveInfo()
+        check(self.lib.pgmg_solve(self.h, C.byref(o), C.byref(info)), "pgmg_solve")
+        info.history = self.history()
+        return info
+
+    def history(self):
+        """The last solve's checks: [(cycles run before the check, res, rel_error), ...]."""
+        n = C.c_int()
+        check(self.lib.pgmg_history(self.h, 0, None, None, None, C.byref(n)), "pgmg_history")
+        k = n.value
+        cyc, res, rel = (C.c_int * k)(), (C.c_double * k)(), (C.c_double * k)()
+        check(self.lib.pgmg_history(self.h, k, cyc, res, rel, C.byref(n)), "pgmg_history")
+        return [(cyc[i], res[i], rel[i]) for i in range(k)]
 
     def stats(self):
         s, e = C.c_longlong(), C.c_longlong()

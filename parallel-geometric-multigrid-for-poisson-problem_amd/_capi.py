@@ -46,6 +46,16 @@ PGMG_FLAG_NO_SPIN = 1048576
 PGMG_PRECISION_FP64 = 0
 PGMG_PRECISION_FP32 = 1
 
+PGMG_MON_RESIDUAL = 1
+PGMG_MON_ERROR = 2
+PGMG_CYCLE_V = 0
+PGMG_CYCLE_W = 1
+PGMG_CYCLE_F = 2
+PGMG_STOP_CONVERGED = 1
+PGMG_STOP_MAX_CYCLES = 2
+PGMG_STOP_STALLED = 3
+PGMG_STOP_NONFINITE = 4
+
 
 # pgmg_host_transport (include/pgmg.h): the caller's message functions
 HT_EXCHANGE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p),
@@ -87,6 +97,23 @@ class PgmgConfig(C.Structure):
     ]
 
 
+class PgmgMonitorOut(C.Structure):
+    _fields_ = [("res_norm", C.c_double), ("err_norm", C.c_double), ("exact_norm", C.c_double),
+                ("rel_error", C.c_double)]
+
+
+class PgmgSolveOpts(C.Structure):
+    _fields_ = [("cycle", C.c_int), ("max_cycles", C.c_int), ("check_every", C.c_int),
+                ("rtol", C.c_double), ("atol", C.c_double), ("stall_ratio", C.c_double),
+                ("stall_checks", C.c_int), ("monitor", C.c_uint)]
+
+
+class PgmgSolveInfo(C.Structure):
+    _fields_ = [("cycles", C.c_int), ("checks", C.c_int), ("reason", C.c_int),
+                ("res0", C.c_double), ("res", C.c_double), ("rel_error", C.c_double),
+                ("elapsed_ms", C.c_double)]
+
+
 # (name, restype, argtypes) for every symbol include/pgmg.h declares
 _P = C.c_void_p
 _DP = C.POINTER(C.c_double)
@@ -109,6 +136,11 @@ SIGNATURES = [
     ("pgmg_gather_solution", C.c_int, [_P, C.c_int, _P]),
     ("pgmg_solution_hash", C.c_int, [_P, C.c_int, C.POINTER(C.c_ulonglong)]),
     ("pgmg_residual_norm", C.c_int, [_P, _DP]),
+    ("pgmg_monitor", C.c_int, [_P, C.c_uint, C.POINTER(PgmgMonitorOut)]),
+    ("pgmg_monitor_time", C.c_int, [_P, C.c_uint, C.c_int, _DP, _DP]),
+    ("pgmg_solve_opts_default", C.c_int, [C.POINTER(PgmgSolveOpts)]),
+    ("pgmg_solve", C.c_int, [_P, C.POINTER(PgmgSolveOpts), C.POINTER(PgmgSolveInfo)]),
+    ("pgmg_history", C.c_int, [_P, C.c_int, C.POINTER(C.c_int), _DP, _DP, C.POINTER(C.c_int)]),
     ("pgmg_stats", C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     ("pgmg_stats_detail", C.c_int, [_P, C.POINTER(C.c_longlong)]),
     ("pgmg_last_elapsed_ms", C.c_int, [_P, _DP]),

@@ -222,6 +222,20 @@ struct pgmg_ctx {
     // pre-smooth) when no entry touched the problem in between
     bool carry = false;           // lv[1].F holds the validated restriction of lv[0].A's pre-smooth
     long long carry_n[3] = {0, 0, 0};   // calls that took a carry, carries made, dropped
+    // the convergence monitor (pgmg_monitor.hip): an analytic problem's unscaled sine tables
+    // sx[i], sy[j] of the exact solution (uploaded by setup_rhs beside rhs_tab, zero-padded like
+    // it), the per-workgroup partial sums (3 each) followed by the three totals, and the last
+    // pgmg_solve's checks
+    bool analytic = false;        // the problem's f is the analytic RHS (f = NULL at set_problem*)
+    double *mon_tab = nullptr;
+    const double *mon_sx = nullptr, *mon_sy = nullptr;
+    double *mon_buf = nullptr;
+    int mon_cap = 0;              // workgroups mon_buf holds partials for
+    struct SolveRecord {
+        int cycle;
+        double res, rel_error;
+    };
+    std::vector<SolveRecord> solve_hist;
 };
 
 namespace pgmg {

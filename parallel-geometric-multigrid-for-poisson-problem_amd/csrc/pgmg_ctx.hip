@@ -26,6 +26,8 @@
 //   pgmg_spec.hip    "speculative calls": reply_wait and the pinned reply, the per-level policy
 //                    and "predicted to fire", segment planning, run_cycles_spec, its queries
 //   pgmg_fcycle.hip  the F-cycle, "speculative F-cycles", pgmg_fcycle
+//   pgmg_monitor.hip the convergence monitor (its kernel too), pgmg_solve and its history; the
+//                    stop rule itself is the HIP-free pgmg_stop.h
 #include <cxxabi.h>
 
 #include <cmath>
@@ -105,6 +107,8 @@ int pgmg_destroy(pgmg_ctx *c)
     if (c->partials2) (void)hipFree(c->partials2);
     if (c->partials3) (void)hipFree(c->partials3);
     if (c->rhs_tab) (void)hipFree(c->rhs_tab);
+    if (c->mon_tab) (void)hipFree(c->mon_tab);
+    if (c->mon_buf) (void)hipFree(c->mon_buf);
     if (c->fmg_gtab) (void)hipFree(c->fmg_gtab);
     if (c->uflags) (void)hipFree(c->uflags);
     if (c->pin) (void)hipHostFree(c->pin);
@@ -384,6 +388,7 @@ static int setup_rhs(pgmg_ctx *c, const double *f, int r0, int r1)
     int e;
     c->gen_rhs = false;
     c->rgfx = c->rgsy = nullptr;
+    c->analytic = f == nullptr;
     if (f) {
         if ((e = upload_rows(c, L, L.F, f, r0, r1))) return e;
     } else {
@@ -399,6 +404,19 @@ static int setup_rhs(pgmg_ctx *c, const double *f, int r0, int r1)
         HIPC(hipGetLastError());
         PGMG_TRY(stream_wait(c));
         HIPC(hipFree(d));
+        // the exact solution's tables for the monitor's error sums (pgmg_monitor.hip): the
+        // unscaled sx[i], sy[j] (compute_function's product), padded like the tables below
+        {
+            const int nx = 8 + N + 1024, ny = 8 + N + 16;
+            std::vector<double> tab((size_t)nx + ny, 0.0);
+            for (int i = 0; i < N; ++i) tab[8 + i] = sx[i];
+            for (int j = 0; j < N; ++j) tab[(size_t)nx + 8 + j] = sy[j];
+            if (!c->mon_tab) HIPC(hipMalloc((void **)&c->mon_tab, tab.size() * sizeof(double)));
+            HIPC(hipMemcpy(c->mon_tab, tab.data(), tab.size() * sizeof(double),
+                           hipMemcpyHostToDevice));
+            c->mon_sx = c->mon_tab + 8;
+            c->mon_sy = c->mon_tab + nx + 8;
+        }
         // tables for regenerating f inside the level-0 passes: fx[i] = factor * sx[i]
         // (the first product of k_rhs's factor * sx[i] * sy[j]) and sy[j], zero-padded
         // past the grid (columns / rows -8 .. N + 1024 / N + 16, like the stored f's
@@ -475,6 +493,7 @@ int pgmg_set_problem_device(pgmg_ctx *c, double *phi, const double *f)
     } else {
         c->gen_rhs = false;
         c->rgfx = c->rgsy = nullptr;
+        c->analytic = false;
     }
     // in place: a cross-fused fp64 context and phi inside an allocation that covers the rows
     // and columns the finest passes read past the grid (pgmg_alloc_grid's guard)
@@ -532,7 +551,7 @@ static void ext_frames(pgmg_ctx *c)
 // The null stream is the CALLING thread's current device's, so the record runs with the
 // context's device made current (and the caller's restored): one thread may drive contexts on
 // several devices.
-static int order_after_caller(pgmg_ctx *c)
+int pgmg::order_after_caller(pgmg_ctx *c)
 {
     int prev = -1;
     HIPC(hipGetDevice(&prev));

@@ -1032,21 +1032,7 @@ constexpr int pp_depth()
 {
     return sizeof(T) == 4 ? PGMG_F32_DEPTH : ((GENF && !R2 && !(OPT & (64 | 32 | 256))) ? 3 : 2);
 }
-// Lane t's 16-byte (fp32: 8-byte) column pair of a row segment starting at `base`; lanes
-// t >= n read 0 (descriptor range check).  The descriptor is built from wave-uniform values.
-template <class T, int NT>
-__device__ __forceinline__ V2<T> buf_row(const T *base, int n, int t)
-{
-    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<T *>(base), (short)0, n * (int)sizeof(V2<T>), 0x00020000);
-    if constexpr (sizeof(T) == 8) {
-        return __builtin_bit_cast(V2<T>, __builtin_amdgcn_raw_buffer_load_b128(
-                                             r, t * 16, 0, NT ? 2 : 0));
-    } else {
-        return __builtin_bit_cast(V2<T>, __builtin_amdgcn_raw_buffer_load_b64(
-                                             r, t * 8, 0, NT ? 2 : 0));
-    }
-}
+// (buf_row, the row-segment load of a lane's column pair: pgmg_internal.h)
 template <class T, int NT>
 __device__ __forceinline__ void buf_store_row(T *base, int bytes, int off, V2<T> v)
 {

@@ -73,6 +73,8 @@ int run_cycles_spec(pgmg_ctx *c, int ncycles, int gamma);
 // --- pgmg_ctx.hip
 void sine_tables(const pgmg_config &cfg, int N, double h, std::vector<double> &sx,
                  std::vector<double> &sy, double &factor);
+// a device-bound problem: the context's stream starts after the caller's null-stream work
+int order_after_caller(pgmg_ctx *c);
 int ext_stage_in(pgmg_ctx *c, bool inplace);
 int ext_stage_out(pgmg_ctx *c);
 

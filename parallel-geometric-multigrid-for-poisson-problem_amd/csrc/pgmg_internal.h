@@ -92,6 +92,22 @@ constexpr int kBlock = 256;       // threads per block for streaming kernels (4 
 constexpr int kTailThreads = PGMG_TAIL_THREADS;   // the tail workgroup (wave-0 paths fit 128 VGPRs)
 constexpr int kTailMaxN = 65;     // largest level the LDS-resident tail holds
 
+// Lane t's 16-byte (fp32: 8-byte) column pair of a row segment starting at `base`; lanes
+// t >= n read 0 (descriptor range check).  The descriptor is built from wave-uniform values.
+template <class T, int NT>
+__device__ __forceinline__ V2<T> buf_row(const T *base, int n, int t)
+{
+    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<T *>(base), (short)0, n * (int)sizeof(V2<T>), 0x00020000);
+    if constexpr (sizeof(T) == 8) {
+        return __builtin_bit_cast(V2<T>, __builtin_amdgcn_raw_buffer_load_b128(
+                                             r, t * 16, 0, NT ? 2 : 0));
+    } else {
+        return __builtin_bit_cast(V2<T>, __builtin_amdgcn_raw_buffer_load_b64(
+                                             r, t * 8, 0, NT ? 2 : 0));
+    }
+}
+
 // Allocation registry and read/write span checks (DESIGN.md §2 "Read extents").  Every
 // level grid (alloc_grid) is registered; the launch wrappers of the fused passes compute,
 // from the band geometry the kernel itself uses, the first and last row and column they

@@ -1,0 +1,431 @@
+// pgmg_monitor.hip — the convergence monitor and solve-to-tolerance (include/pgmg.h
+// "Convergence monitor and solve-to-tolerance"; DESIGN.md "Convergence monitor").
+//
+// The reference's driver measures convergence after every cycle (MultigridTestRunner::
+// run_cycle, 2_part_MG/MultiGridTestRunner.hpp:190-244: compute_residual + norm, and with
+// flag_err_norm_iteration ||phi - u|| / ||u||, :110-122, :252-254).  Here that is ONE streaming
+// pass over the finest-level iterate, read where it lies, that yields up to three fp64 sums:
+//   sum r^2   interior points of the rows this rank updates,
+//             r = f - ih * (4x - x_l - x_r - x_u - x_d)   (DynamicGridUtils.hpp:59-69's order)
+//   sum e^2   all points of the rows this rank owns, boundary included, e = (double)phi - u
+//   sum u^2   the same points, u = sx[i] * sy[j]           (compute_function's product)
+// shaped like the other level-0 passes (pgmg_kernels.hip): lane t of a wave owns a column pair
+// (one 16-byte row load), a workgroup marches down a band keeping a three-row window in
+// registers (each phi row crosses HBM once per band, plus one halo row at each end), horizontal
+// neighbours come through DPP, and kMonU rows are loaded before any is used.
+//
+// Decomposition (a function of N and the rank's rows [lo, hi) only -- not of pitch, address,
+// which array is bound, or the sums asked for): tiles of kMonTile = 512 columns starting at
+// column 1 (column 0 rides with lane 0 of the first tile), bands of kMonBand = 64 rows starting
+// at row lo.  Every lane adds its terms in row order, the lanes of a wave in wave_sum's fixed
+// tree, the four waves in index order; the workgroups' partials are written with plain stores
+// and added in index order by k_mon_reduce.  No floating-point atomics: the same state gives the
+// same bits.
+#include <chrono>
+#include <cmath>
+#include <limits>
+
+#include "pgmg_host.h"
+#include "pgmg_stop.h"
+
+using namespace pgmg;
+
+namespace pgmg {
+
+constexpr int kMonBand = 64;           // rows per workgroup
+constexpr int kMonTile = 2 * kBlock;   // columns per workgroup (a column pair per lane)
+constexpr int kMonU = 4;               // rows in flight per wave
+
+constexpr unsigned kMonRes = PGMG_MON_RESIDUAL, kMonErr = PGMG_MON_ERROR;
+constexpr unsigned kMonGen = 4u;       // f regenerated from the sine tables (not streamed)
+
+// SX / SF: the element types phi and a stored f are read as (T, or double for the caller's
+// arrays of a device-bound problem, converted on load as launch_from_double converts them)
+template <class T, class SX, class SF>
+struct MonArgsT {
+    const SX *x;             // element (0, 0) of phi, pitch Px
+    const SF *f;             // element (0, 0) of the stored f, pitch Pf (unused with kMonGen)
+    long long Px, Pf;
+    const double *gfx, *gsy; // kMonGen: f = (T)(gfx[i] * gsy[j])
+    const double *sx, *sy;   // kMonErr: u = sx[i] * sy[j]
+    double *partials;        // 3 per workgroup: sum r^2, sum e^2, sum u^2
+    T ih;
+    int N;
+    int lo, hi;              // rows this rank owns (the error sums' rows)
+    int u0, u1;              // interior rows this rank updates (the residual sum's rows)
+};
+
+// a column pair read as S, as the context's element type
+template <class T, class S> __device__ __forceinline__ V2<T> mon_cv(V2<S> v)
+{
+    return mk2<T>((T)v.x, (T)v.y);
+}
+
+template <class T, class SX, class SF, unsigned MODE>
+__global__ __launch_bounds__(kBlock) void k_monitor(MonArgsT<T, SX, SF> a)
+{
+    constexpr bool RES = (MODE & kMonRes) != 0, ERR = (MODE & kMonErr) != 0;
+    constexpr bool GEN = (MODE & kMonGen) != 0;
+    __shared__ double red[3][kBlock / 64];
+    const int lane = threadIdx.x & 63;
+    // (readfirstlane: the wave index, and so every row descriptor, is wave-uniform for the compiler)
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int N = a.N;
+    const int npairs = (N - 1) >> 1;                 // pairs (1+2t, 2+2t) cover columns 1 .. N-1
+    const int p0 = blockIdx.x * kBlock + wave * 64;  // the wave's first pair
+    const int nw = min(max(npairs - p0, 0), 64);     // its pairs
+    const int cw = 1 + 2 * p0;                       // its first column
+    const int c = cw + 2 * lane;                     // this lane's columns c, c + 1
+    const bool act = lane < nw;
+    const bool second = c + 1 <= N - 2;              // else column c + 1 is the right boundary
+    const bool has_right = cw + 128 <= N - 1;        // lane 63 has a neighbour column in the row
+    const int jb = a.lo + blockIdx.y * kMonBand;
+    const int je = min(jb + kMonBand, a.hi);
+    const long long Px = a.Px, Pf = a.Pf;
+    const SX *__restrict__ X = a.x;
+    const SF *__restrict__ F = a.f;
+    const T ih = a.ih;
+    using D2 = V2<T>;
+    double accr = 0.0, acce = 0.0, accu = 0.0;
+
+    if (nw > 0) {   // (wave-uniform; a wave past the last column only joins the block sum)
+        double fx0 = 0.0, fx1 = 0.0, sx0 = 0.0, sx1 = 0.0, sxl = 0.0;
+        if (RES && GEN && act) {
+            fx0 = a.gfx[c];
+            fx1 = a.gfx[c + 1];
+        }
+        if (ERR && act) {
+            sx0 = a.sx[c];
+            sx1 = a.sx[c + 1];
+            sxl = a.sx[0];
+        }
+        // rows are clamped into the grid: a clamped row only feeds residuals of rows outside
+        // [u0, u1), which are not summed
+        auto rowx = [&](int r) -> D2 {
+            r = min(max(r, 0), N - 1);
+            return mon_cv<T, SX>(buf_row<SX, 0>(X + r * Px + cw, nw, lane));
+        };
+        D2 w0 = zero2<T>(), w1;
+        if (RES) w0 = rowx(jb - 1);
+        w1 = rowx(jb);
+        for (int j = jb; j < je; j += kMonU) {
+            D2 xn[kMonU], fv[kMonU];
+            T el[kMonU], er[kMonU];
+            #pragma unroll
+            for (int u = 0; u < kMonU; ++u) {
+                const int r = min(j + u, je - 1);
+                xn[u] = rowx(r + 1);
+                if (RES && !GEN) fv[u] = mon_cv<T, SF>(buf_row<SF, 0>(F + r * Pf + cw, nw, lane));
+                else fv[u] = zero2<T>();
+                el[u] = T(0);
+                er[u] = T(0);
+                if (lane == 0) el[u] = (T)X[r * Px + cw - 1];
+                if (RES && lane == 63 && has_right) er[u] = (T)X[r * Px + cw + 128];
+            }
+            #pragma unroll
+            for (int u = 0; u < kMonU; ++u) {
+                const int r = j + u;
+                const D2 up = (u == 0) ? w0 : (u == 1 ? w1 : xn[u - 2]);
+                const D2 ce = (u == 0) ? w1 : xn[u - 1];
+                const D2 dn = xn[u];
+                const bool live = act && r < je;
+                if (RES) {
+                    T left = dpp_shr(ce.y);
+                    T right = dpp_shl(ce.x);
+                    if (lane == 0) left = el[u];
+                    if (lane == 63) right = er[u];
+                    D2 fr = fv[u];
+                    if (GEN) {
+                        const double sy = a.gsy[min(r, N - 1)];
+                        fr = mk2<T>((T)(fx0 * sy), (T)(fx1 * sy));
+                    }
+                    const T r0 = fr.x - ih * (T(4) * ce.x - left - ce.y - up.x - dn.x);
+                    const T r1 = fr.y - ih * (T(4) * ce.y - ce.x - right - up.y - dn.y);
+                    if (live && r >= a.u0 && r < a.u1) {
+                        accr += sq(r0);
+                        if (second) accr += sq(r1);
+                    }
+                }
+                if (ERR) {
+                    const double sy = a.sy[min(r, N - 1)];
+                    const double u0v = sx0 * sy, u1v = sx1 * sy;
+                    const double e0 = (double)ce.x - u0v, e1 = (double)ce.y - u1v;
+                    if (live) {
+                        acce += e0 * e0;
+                        accu += u0v * u0v;
+                        acce += e1 * e1;
+                        accu += u1v * u1v;
+                        if (lane == 0 && cw == 1) {   // column 0
+                            const double ul = sxl * sy, elv = (double)el[u] - ul;
+                            acce += elv * elv;
+                            accu += ul * ul;
+                        }
+                    }
+                }
+            }
+            w0 = xn[kMonU - 2];
+            w1 = xn[kMonU - 1];
+        }
+    }
+    const double sr = wave_sum(accr), se = wave_sum(acce), su = wave_sum(accu);
+    if (lane == 0) {
+        red[0][wave] = sr;
+        red[1][wave] = se;
+        red[2][wave] = su;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        double s = 0.0;
+        #pragma unroll
+        for (int w = 0; w < kBlock / 64; ++w) s += red[threadIdx.x][w];
+        a.partials[3 * (size_t)(blockIdx.y * gridDim.x + blockIdx.x) + threadIdx.x] = s;
+    }
+}
+
+// out[q] = sum over the np workgroups of partials[3 k + q], in a fixed order
+__global__ __launch_bounds__(kBlock) void k_mon_reduce(const double *partials, int np, double *out)
+{
+    __shared__ double red[3][kBlock / 64];
+    double s[3] = {0.0, 0.0, 0.0};
+    for (int k = threadIdx.x; k < np; k += kBlock) {
+        #pragma unroll
+        for (int q = 0; q < 3; ++q) s[q] += partials[3 * (size_t)k + q];
+    }
+    #pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const double v = wave_sum(s[q]);
+        if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        double t = 0.0;
+        #pragma unroll
+        for (int w = 0; w < kBlock / 64; ++w) t += red[threadIdx.x][w];
+        out[threadIdx.x] = t;
+    }
+}
+
+struct MonGrid {
+    int tiles, bands;
+};
+static MonGrid mon_grid(int N, int lo, int hi)
+{
+    return {(N - 1 + kMonTile - 1) / kMonTile, (hi - lo + kMonBand - 1) / kMonBand};
+}
+
+template <class T, class SX, class SF>
+static void mon_launch_mode(const MonArgsT<T, SX, SF> &a, unsigned mode, dim3 g, hipStream_t s)
+{
+    switch (mode) {
+    case kMonRes: k_monitor<T, SX, SF, kMonRes><<<g, dim3(kBlock), 0, s>>>(a); break;
+    case kMonRes | kMonGen: k_monitor<T, SX, SF, kMonRes | kMonGen><<<g, dim3(kBlock), 0, s>>>(a); break;
+    case kMonErr: k_monitor<T, SX, SF, kMonErr><<<g, dim3(kBlock), 0, s>>>(a); break;
+    case kMonRes | kMonErr: k_monitor<T, SX, SF, kMonRes | kMonErr><<<g, dim3(kBlock), 0, s>>>(a); break;
+    default: k_monitor<T, SX, SF, kMonRes | kMonErr | kMonGen><<<g, dim3(kBlock), 0, s>>>(a); break;
+    }
+}
+
+// Enqueue the pass and the reduction of its partials: the three totals land in c->mon_buf +
+// 3 * c->mon_cap.  phi and f are read where they lie: the level-0 grids, or the caller's arrays
+// of a device-bound problem (pitch N, double).
+template <class T>
+static int mon_enqueue(pgmg_ctx *c, unsigned what)
+{
+    const Level &L = c->lv[0];
+    const MonGrid mg = mon_grid(L.N, L.lo, L.hi);
+    const int np = mg.tiles * mg.bands;
+    if (np > c->mon_cap) {
+        if (c->mon_buf) HIPC(hipFree(c->mon_buf));
+        c->mon_buf = nullptr;
+        c->mon_cap = 0;
+        if (hipMalloc((void **)&c->mon_buf, sizeof(double) * 3 * ((size_t)np + 1)) != hipSuccess)
+            return set_err(PGMG_ERR_NOMEM, "monitor partials");
+        c->mon_cap = np;
+    }
+    const bool res = (what & kMonRes) != 0;
+    const bool gen = res && c->ext_f == nullptr && c->gen_rhs;
+    const unsigned mode = what | (gen ? kMonGen : 0u);
+    const dim3 g(mg.tiles, mg.bands);
+    double *out = c->mon_buf + 3 * (size_t)c->mon_cap;
+    auto fill = [&](auto &a) {
+        a.gfx = c->gfx;
+        a.gsy = c->gsy;
+        a.sx = c->mon_sx;
+        a.sy = c->mon_sy;
+        a.partials = c->mon_buf;
+        a.ih = (T)L.ih;
+        a.N = L.N;
+        a.lo = L.lo;
+        a.hi = L.hi;
+        a.u0 = L.u0;
+        a.u1 = L.u1;
+    };
+    if (c->ext_phi == nullptr) {
+        MonArgsT<T, T, T> a{};
+        a.x = G<T>(L.A);
+        a.Px = L.P;
+        a.f = G<T>(L.F);
+        a.Pf = L.P;
+        fill(a);
+        mon_launch_mode(a, mode, g, c->s);
+    } else if (c->ext_f != nullptr) {
+        MonArgsT<T, double, double> a{};
+        a.x = c->ext_phi;
+        a.Px = L.N;
+        a.f = c->ext_f;
+        a.Pf = L.N;
+        fill(a);
+        mon_launch_mode(a, mode, g, c->s);
+    } else {   // the analytic f: regenerated, or the context's stored copy
+        MonArgsT<T, double, T> a{};
+        a.x = c->ext_phi;
+        a.Px = L.N;
+        a.f = G<T>(L.F);
+        a.Pf = L.P;
+        fill(a);
+        mon_launch_mode(a, mode, g, c->s);
+    }
+    k_mon_reduce<<<dim3(1), dim3(kBlock), 0, c->s>>>(c->mon_buf, np, out);
+    HIPC(hipGetLastError());
+    return PGMG_OK;
+}
+
+static int mon_check(pgmg_ctx *c, unsigned what)
+{
+    if (what == 0 || (what & ~(kMonRes | kMonErr))) return set_err(PGMG_ERR_ARG, "bad monitor bits");
+    if (!c->have_problem) return set_err(PGMG_ERR_STATE, "pgmg_set_problem first");
+    if (!c->lv[0].on_this_rank) return set_err(PGMG_ERR_STATE, "level 0 not on this rank");
+    if ((what & kMonErr) && !c->analytic)
+        return set_err(PGMG_ERR_STATE, "PGMG_MON_ERROR needs the analytic problem (f = NULL): the "
+                                       "exact solution of a caller's f is not known");
+    return PGMG_OK;
+}
+
+// the three sums of the current iterate on the host (synchronous; collective on row strips)
+static int mon_sums(pgmg_ctx *c, unsigned what, double sums[3])
+{
+    const Level &L = c->lv[0];
+    if (c->ext_phi) PGMG_TRY(order_after_caller(c));
+    if (c->comm && (what & kMonRes)) PGMG_TRY(c->comm->halo(L.A, L, 1, c->s));
+    PGMG_TRY(c->fp32 ? mon_enqueue<float>(c, what) : mon_enqueue<double>(c, what));
+    double *out = c->mon_buf + 3 * (size_t)c->mon_cap;
+    if (c->comm) PGMG_TRY(c->comm->allreduce_sum(out, 3, c->s));
+    HIPC(hipMemcpyAsync(sums, out, 3 * sizeof(double), hipMemcpyDeviceToHost, c->s));
+    PGMG_TRY(stream_wait(c));
+    return PGMG_OK;
+}
+
+static int mon_run(pgmg_ctx *c, unsigned what, pgmg_monitor_out *o)
+{
+    double s[3] = {0.0, 0.0, 0.0};
+    PGMG_TRY(mon_sums(c, what, s));
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    o->res_norm = (what & kMonRes) ? std::sqrt(s[0]) : nan;
+    o->err_norm = (what & kMonErr) ? std::sqrt(s[1]) : nan;
+    o->exact_norm = (what & kMonErr) ? std::sqrt(s[2]) : nan;
+    o->rel_error = (what & kMonErr) ? std::sqrt(s[1]) / std::sqrt(s[2]) : nan;   // orc_rel_error's form
+    return PGMG_OK;
+}
+
+}  // namespace pgmg
+
+extern "C" {
+
+int pgmg_monitor(pgmg_ctx *c, unsigned what, pgmg_monitor_out *out)
+{
+    if (!c || !out) return set_err(PGMG_ERR_ARG, "null argument");
+    PGMG_TRY(mon_check(c, what));
+    return mon_run(c, what, out);
+}
+
+int pgmg_monitor_time(pgmg_ctx *c, unsigned what, int reps, double *ms, double *bytes)
+{
+    if (!c || !ms || reps <= 0) return set_err(PGMG_ERR_ARG, "bad argument");
+    PGMG_TRY(mon_check(c, what));
+    if (c->comm) return set_err(PGMG_ERR_STATE, "pgmg_monitor_time: one GPU only (world 1)");
+    auto run = [&]() { return c->fp32 ? mon_enqueue<float>(c, what) : mon_enqueue<double>(c, what); };
+    if (c->ext_phi) PGMG_TRY(order_after_caller(c));
+    for (int k = 0; k < 2; ++k) PGMG_TRY(run());
+    HIPC(hipEventRecord(c->ev0, c->s));
+    for (int k = 0; k < reps; ++k) PGMG_TRY(run());
+    HIPC(hipEventRecord(c->ev1, c->s));
+    HIPC(hipEventSynchronize(c->ev1));
+    float f = 0.f;
+    HIPC(hipEventElapsedTime(&f, c->ev0, c->ev1));
+    *ms = f / reps;
+    if (bytes) {
+        const Level &L = c->lv[0];
+        const bool stored = (what & kMonRes) && !(c->ext_f == nullptr && c->gen_rhs);
+        const double xb = c->ext_phi ? 8.0 : L.es, fb = c->ext_f ? 8.0 : L.es;
+        *bytes = xb * (double)L.N * L.N + (stored ? fb * (double)(L.N - 2) * (L.N - 2) : 0.0);
+    }
+    return PGMG_OK;
+}
+
+int pgmg_solve_opts_default(pgmg_solve_opts *o)
+{
+    if (!o) return set_err(PGMG_ERR_ARG, "null opts");
+    *o = pgmg_solve_opts{};
+    o->cycle = PGMG_CYCLE_V;
+    o->max_cycles = 30;
+    o->check_every = 1;
+    o->rtol = 1e-3;
+    o->atol = 0.0;
+    o->stall_ratio = 0.0;
+    o->stall_checks = 2;
+    o->monitor = PGMG_MON_RESIDUAL;
+    return PGMG_OK;
+}
+
+int pgmg_solve(pgmg_ctx *c, const pgmg_solve_opts *o, pgmg_solve_info *info)
+{
+    if (!c || !o || !info) return set_err(PGMG_ERR_ARG, "null argument");
+    if (const char *bad = solve_opts_error(*o)) return set_err(PGMG_ERR_ARG, std::string("pgmg_solve: ") + bad);
+    const unsigned what = o->monitor | PGMG_MON_RESIDUAL;
+    PGMG_TRY(mon_check(c, what));
+    const auto t0 = std::chrono::steady_clock::now();
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    c->solve_hist.clear();
+    *info = pgmg_solve_info{};
+    info->rel_error = nan;
+    StopState st;
+    int cycles = 0;
+    for (;;) {
+        pgmg_monitor_out m{};
+        PGMG_TRY(mon_run(c, what, &m));
+        c->solve_hist.push_back({cycles, m.res_norm, m.rel_error});
+        int next = 0;
+        const int reason = stop_check(*o, st, cycles, m.res_norm, &next);
+        info->cycles = cycles;
+        info->checks = st.checks;
+        info->res0 = st.r0;
+        info->res = m.res_norm;
+        info->rel_error = m.rel_error;
+        if (reason) {
+            info->reason = reason;
+            break;
+        }
+        PGMG_TRY(o->cycle == PGMG_CYCLE_V   ? pgmg_vcycle(c, next)
+                 : o->cycle == PGMG_CYCLE_W ? pgmg_wcycle(c, next)
+                                            : pgmg_fcycle(c, next));
+        cycles += next;
+    }
+    info->elapsed_ms =
+        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return PGMG_OK;
+}
+
+int pgmg_history(pgmg_ctx *c, int cap, int *cycle, double *res, double *rel_error, int *n)
+{
+    if (!c || !n || cap < 0) return set_err(PGMG_ERR_ARG, "bad argument");
+    const int have = (int)c->solve_hist.size();
+    *n = have;
+    for (int i = 0; i < have && i < cap; ++i) {
+        if (cycle) cycle[i] = c->solve_hist[i].cycle;
+        if (res) res[i] = c->solve_hist[i].res;
+        if (rel_error) rel_error[i] = c->solve_hist[i].rel_error;
+    }
+    return PGMG_OK;
+}
+
+}  // extern "C"

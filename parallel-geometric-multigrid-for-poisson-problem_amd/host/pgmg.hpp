@@ -96,6 +96,27 @@ class Context {
     Context(const Context &) = delete;
     Context &operator=(const Context &) = delete;
     pgmg_ctx *get() const { return c_; }
+    // one pass over the current iterate (PGMG_MON_* bits): norms of the residual and, for an
+    // analytic problem, of the error against the exact solution
+    pgmg_monitor_out monitor(unsigned what = PGMG_MON_RESIDUAL) const
+    {
+        pgmg_monitor_out o{};
+        check(pgmg_monitor(c_, what, &o), "pgmg_monitor");
+        return o;
+    }
+    static pgmg_solve_opts solve_defaults()
+    {
+        pgmg_solve_opts o{};
+        check(pgmg_solve_opts_default(&o), "pgmg_solve_opts_default");
+        return o;
+    }
+    // cycle until the stop rule of include/pgmg.h ends the solve
+    pgmg_solve_info solve(const pgmg_solve_opts &o) const
+    {
+        pgmg_solve_info info{};
+        check(pgmg_solve(c_, &o, &info), "pgmg_solve");
+        return info;
+    }
 
   private:
     pgmg_ctx *c_ = nullptr;
