@@ -357,6 +357,53 @@ int pgmg_solve(pgmg_ctx *ctx, const pgmg_solve_opts *o, pgmg_solve_info *info);
  * of the arrays may be NULL. */
 int pgmg_history(pgmg_ctx *ctx, int cap, int *cycle, double *res, double *rel_error, int *n);
 
+/* ---- Full multigrid for the problem's own right-hand side -------------------------------
+ * pgmg_fcycle is the reference's F-cycle: it rebuilds the ANALYTIC right-hand side on every
+ * level, so a caller who passed an f of their own gets the answer to another problem.
+ * pgmg_fmg(ctx, nu) replaces phi with the full-multigrid solution of the context's problem:
+ *   levels  N_0 = N, N_{l+1} = (N_l - 1) / 2 + 1 down to the first N_L <= n_coarse;
+ *           h_l = h_0 * 2^l (h_0: pgmg_config.h0, or a / (N - 1)).
+ *   1. f_0 is the problem's level-0 right-hand side as stored: the caller's f, or the analytic
+ *      RHS that pgmg_set_problem*(.., NULL) keeps.  f_{l+1} = full weighting of f_l on the
+ *      interior points (1/4 centre + 1/8 edges + 1/16 corners, the order of compute_coarsest_grid,
+ *      MultiGrid.hpp:28-55), boundary 0.
+ *   2. u_L = 0, then nu x v_cycle(u_L, f_L, N_L, h_L) (MultiGrid.hpp:57-94; at N <= n_coarse
+ *      that is the coarsest smoother call, coarse_iter + 1 sweeps).
+ *   3. for l = L-1 .. 0: u_l = C(u_{l+1}), then nu x v_cycle(u_l, f_l, N_l, h_l).
+ *   The current phi (boundary included) is ignored and overwritten with u_0, whose boundary
+ *   is 0; f is left untouched.
+ * C is the tensor-product cubic interpolation from Nc to Nf = 2 Nc - 1 points per side, every
+ * fine point assigned: first along x on every coarse row, then along y on the x-interpolated
+ * rows.  Along one line c[0 .. Nc-1] -> fine[0 .. Nf-1]:
+ *   fine[2i]   = c[i]
+ *   fine[k]    = (9.0 * (b + c) - (a + d)) * 0.0625            odd k, 3 <= k <= Nf-4, with
+ *                a, b, c, d = c[(k-3)/2], c[(k-1)/2], c[(k+1)/2], c[(k+3)/2]
+ *   fine[1]    = (5.0 * c[0] + 15.0 * c[1] - 5.0 * c[2] + c[3]) * 0.0625
+ *   fine[Nf-2] = (5.0 * c[Nc-1] + 15.0 * c[Nc-2] - 5.0 * c[Nc-3] + c[Nc-4]) * 0.0625
+ * evaluated left to right in the context's element type, one rounding per operation (no fused
+ * multiply-add).  This needs N_L >= 5: with n_coarse < 5 (N_L = 3) the call returns
+ * PGMG_ERR_ARG.  N = 5 is legal (no climb, step 2 only).  Bilinear interpolation would not do:
+ * with a second-order discretisation its FMG error grows with N relative to the discretisation
+ * error; cubic with nu = 2 lands at 0.9 x the discretisation error at every size
+ * (tests/test_fmg_cpu.py) for about 8/3 finest-level V-cycles of work.
+ * nu < 1 or a null context: PGMG_ERR_ARG.  Before pgmg_set_problem*: PGMG_ERR_STATE.  world > 1:
+ * PGMG_ERR_STATE -- row strips are NOT supported by this entry (one GPU only).  fp64 and fp32
+ * contexts; problems set with pgmg_set_problem and pgmg_set_problem_device (the result lands in
+ * the caller's phi: the climb runs on the context's grids and is copied out, synchronous like
+ * pgmg_fcycle on a bound problem).  Every early-exit check is decided in-stream, so results and
+ * the sweep count are the model's; the call is asynchronous on the context's stream otherwise.
+ * It is an entry that changes phi: it drops the carry and resets the speculation history as
+ * pgmg_set_problem does; the sweep and early-exit statistics continue.  A later pgmg_vcycle /
+ * pgmg_wcycle / pgmg_solve continues from u_0.  pgmg_last_elapsed_ms reports the call's device
+ * time.  The restricted f chain and the grids of the levels below the tail's top are allocated
+ * on the first call (about 1/3 of a level-0 grid). */
+int pgmg_fmg(pgmg_ctx *ctx, int nu);
+/* Measurement: `reps` cubic interpolation passes level 1 -> level 0 back to back on the
+ * context's stream between two hipEvents, after two warm ones; mean device ms per pass and its
+ * algorithmic bytes (one element per fine point written + one per coarse point read).  Needs
+ * N >= 9, world 1.  Leaves phi changed (call set_problem again before parity checks). */
+int pgmg_fmg_interp_time(pgmg_ctx *ctx, int reps, double *ms_per_pass, double *bytes);
+
 /* Cumulative smoother sweeps and early exits since set_problem
  * (comparable with the oracle's counters). */
 int pgmg_stats(pgmg_ctx *ctx, long long *sweeps, long long *early_exits);

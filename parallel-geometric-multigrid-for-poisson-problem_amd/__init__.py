@@ -24,7 +24,7 @@ from ._capi import (PGMG_FLAG_LOOPBACK, PGMG_FLAG_NO_CROSS, PGMG_FLAG_NO_GRAPH,
                     PGMG_FLAG_NO_R2, PGMG_FLAG_HOST_TRANSPORT, PGMG_FLAG_FAST,
                     PGMG_FLAG_NO_SPEC_FIRE, PGMG_FLAG_NO_CTILE, PGMG_FLAG_NO_CARRY, PGMG_FLAG_TIME_COMM, PGMG_FLAG_NO_SHUFFLE, PGMG_FLAG_NO_SPIN,
                     PGMG_PROLONG_REFERENCE,
-                    PGMG_PROLONG_SYMMETRIC, PGMG_OK, PGMG_ERR_STATE, PgmgConfig, PgmgError,
+                    PGMG_PROLONG_SYMMETRIC, PGMG_OK, PGMG_ERR_ARG, PGMG_ERR_STATE, PgmgConfig, PgmgError,
                     PGMG_MON_RESIDUAL, PGMG_MON_ERROR, PGMG_CYCLE_V, PGMG_CYCLE_W, PGMG_CYCLE_F,
                     PGMG_STOP_CONVERGED, PGMG_STOP_MAX_CYCLES, PGMG_STOP_STALLED,
                     PGMG_STOP_NONFINITE, PgmgMonitorOut, PgmgSolveOpts, PgmgSolveInfo,
@@ -229,6 +229,27 @@ class Solver:
 
     def fcycle(self, n=1):
         check(self.lib.pgmg_fcycle(self.h, int(n)), "pgmg_fcycle")
+
+    def fmg(self, nu=2):
+        """Replace phi with the full-multigrid solution of the problem's own right-hand side
+        (pgmg_fmg): f restricted down the pyramid, the coarsest level solved from zero, then per
+        level the cubic interpolation of the coarser solution and `nu` V-cycles.  The current
+        phi is ignored.  With nu=2 the result is at the discretisation error for about 8/3
+        finest-level V-cycles of work, so a solve that starts from it needs few cycles::
+
+            s.set_problem(None, f); s.fmg(); s.solve(rtol=1e-8)
+
+        One GPU only."""
+        check(self.lib.pgmg_fmg(self.h, int(nu)), "pgmg_fmg")
+
+    def fmg_interp_time(self, reps=20):
+        """(mean device ms, algorithmic bytes) of the cubic interpolation pass level 1 ->
+        level 0 over `reps` back to back (pgmg_fmg_interp_time; measurement, leaves phi
+        changed)."""
+        ms, b = C.c_double(), C.c_double()
+        check(self.lib.pgmg_fmg_interp_time(self.h, int(reps), C.byref(ms), C.byref(b)),
+              "pgmg_fmg_interp_time")
+        return ms.value, b.value
 
     def sync(self):
         check(self.lib.pgmg_sync(self.h), "pgmg_sync")

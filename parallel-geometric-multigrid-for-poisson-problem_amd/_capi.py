@@ -141,6 +141,8 @@ SIGNATURES = [
     ("pgmg_solve_opts_default", C.c_int, [C.POINTER(PgmgSolveOpts)]),
     ("pgmg_solve", C.c_int, [_P, C.POINTER(PgmgSolveOpts), C.POINTER(PgmgSolveInfo)]),
     ("pgmg_history", C.c_int, [_P, C.c_int, C.POINTER(C.c_int), _DP, _DP, C.POINTER(C.c_int)]),
+    ("pgmg_fmg", C.c_int, [_P, C.c_int]),
+    ("pgmg_fmg_interp_time", C.c_int, [_P, C.c_int, _DP, _DP]),
     ("pgmg_stats", C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     ("pgmg_stats_detail", C.c_int, [_P, C.POINTER(C.c_longlong)]),
     ("pgmg_last_elapsed_ms", C.c_int, [_P, _DP]),

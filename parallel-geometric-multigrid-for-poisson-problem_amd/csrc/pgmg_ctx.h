@@ -236,6 +236,12 @@ struct pgmg_ctx {
         double res, rel_error;
     };
     std::vector<SolveRecord> solve_hist;
+    // pgmg_fmg (pgmg_fmg.hip), allocated on its first call: the geometry of FMG level l (0 .. nb
+    // the context's own levels, then the halving continued to the first N <= n_coarse), the
+    // restricted right-hand side f_l of every level l >= 1, and the solution grids of the
+    // levels below the tail's top (l > nb; the others use lv[l].A)
+    std::vector<pgmg::Level> fmg_lv;
+    std::vector<pgmg::Grid> fmg_F, fmg_U;
 };
 
 namespace pgmg {

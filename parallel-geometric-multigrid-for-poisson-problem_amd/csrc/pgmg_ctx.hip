@@ -28,6 +28,8 @@
 //   pgmg_fcycle.hip  the F-cycle, "speculative F-cycles", pgmg_fcycle
 //   pgmg_monitor.hip the convergence monitor (its kernel too), pgmg_solve and its history; the
 //                    stop rule itself is the HIP-free pgmg_stop.h
+//   pgmg_fmg.hip     full multigrid for the problem's own f: the cubic interpolation pass (its
+//                    kernel too), the restricted f chain, the climb, pgmg_fmg
 #include <cxxabi.h>
 
 #include <cmath>
@@ -122,6 +124,8 @@ int pgmg_destroy(pgmg_ctx *c)
     free_grid(c->S);
     free_grid(c->Ffmg);
     for (auto &g : c->Ffmg_l) free_grid(g);
+    for (auto &g : c->fmg_F) free_grid(g);
+    for (auto &g : c->fmg_U) free_grid(g);
     if (c->fmg_tab) (void)hipFree(c->fmg_tab);
     if (c->flags) (void)hipFree(c->flags);
     if (c->stats) (void)hipFree(c->stats);
