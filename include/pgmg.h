@@ -167,9 +167,14 @@ typedef struct pgmg_host_transport {
 typedef struct pgmg_config {
     int N;             /* points per side incl. boundary; 2^k + 1, k >= 2        */
     int v1, v2;        /* pre/post smoother num_iter (v+1 sweeps), default 1, 1  */
-    int coarse_iter;   /* num_iter on the coarsest grid, default 10 (11 sweeps)  */
-    int n_coarse;      /* recursion floor N_coarse, default 5                    */
-    int alpha;         /* W-cycle recursion count, default 3                     */
+    int coarse_iter;   /* num_iter on the coarsest grid, default 10 (11 sweeps); >= 0 */
+    int n_coarse;      /* recursion floor N_coarse, default 5; >= 3.  The coarsest level,
+                          the first N_l = (N_{l-1} - 1) / 2 + 1 with N_l <= n_coarse, runs in
+                          the one-workgroup tail and may have at most 65 points per side:
+                          pgmg_create returns PGMG_ERR_ARG otherwise (N 257 with n_coarse 129
+                          or 200; N 257 with 100, 65 with 1000, 33 with 33 are legal)      */
+    int alpha;         /* W-cycle recursion count, default 3; 1 .. 15 (the tail counts a
+                          level's visits in 4 bits): pgmg_create returns PGMG_ERR_ARG above */
     double eps;        /* smoother early-exit tolerance, default 1e-7; <0: never */
     double a, p, q;    /* domain edge and RHS wave numbers, default 1, 1, 1      */
     int tail_n;        /* levels with N <= tail_n run in one workgroup (<= 65)   */
@@ -404,8 +409,10 @@ int pgmg_fmg(pgmg_ctx *ctx, int nu);
  * N >= 9, world 1.  Leaves phi changed (call set_problem again before parity checks). */
 int pgmg_fmg_interp_time(pgmg_ctx *ctx, int reps, double *ms_per_pass, double *bytes);
 
-/* Cumulative smoother sweeps and early exits since set_problem
- * (comparable with the oracle's counters). */
+/* Cumulative smoother sweeps and early exits since set_problem.  The sweeps are the
+ * oracle's.  The early exits are those that cut a smoother call short: the check after a
+ * call's last sweep cannot change the result and is not evaluated, so where the oracle's
+ * early_exits also counts such a check firing (its last_exits), this counter does not. */
 int pgmg_stats(pgmg_ctx *ctx, long long *sweeps, long long *early_exits);
 
 /* [0] sweeps, [1] early exits, [2] k_postpre post-check rare paths taken (-1 when

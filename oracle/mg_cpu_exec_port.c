@@ -16,7 +16,7 @@
 
 typedef struct orc_ctx {
     double eps;
-    int n_coarse, v1, v2, coarse_iter, alpha;
+    int n_coarse, v1, v2, coarse_iter, alpha, last_exits;
     double a, p, q;
     long long sweeps, early_exits, smooth_calls;
 } orc_ctx;

@@ -22,6 +22,7 @@ class OrcCtx(C.Structure):
         ("v2", C.c_int),
         ("coarse_iter", C.c_int),
         ("alpha", C.c_int),
+        ("last_exits", C.c_int),   # in the alignment hole before `a`: the size is unchanged
         ("a", C.c_double),
         ("p", C.c_double),
         ("q", C.c_double),
@@ -106,6 +107,17 @@ class Oracle:
     @property
     def early_exits(self):
         return self.c.early_exits
+
+    @property
+    def smooth_calls(self):
+        return self.c.smooth_calls
+
+    @property
+    def cut_exits(self):
+        """Early exits that cut a smoother call short: what pgmg_stats counts.  early_exits
+        also counts a check that fires after a call's last sweep, which the library never
+        evaluates (it cannot change the result)."""
+        return self.c.early_exits - self.c.last_exits
 
     def rhs(self, N, h=None):
         h = 1.0 / (N - 1) * self.c.a if h is None else h

@@ -56,6 +56,11 @@ typedef struct orc_ctx {
     int v1, v2;        /* pre/post smoothing num_iter (MultiGrid.hpp:15-16)       */
     int coarse_iter;   /* num_iter on the coarsest grid (MultiGrid.hpp:61 -> 10)  */
     int alpha;         /* W-cycle recursions (main.cpp:15 -> 3)                   */
+    /* early exits whose check followed the call's LAST sweep (it == num_iter): they end
+     * nothing early.  The library never evaluates that check (it cannot change the result),
+     * so pgmg_stats' early exits equal early_exits - last_exits.  An int in what was the
+     * alignment hole before `a`: the struct's size and every other offset stay as they were. */
+    int last_exits;
     double a, p, q;    /* problem constants (globals.cpp:2-4)                     */
     /* statistics */
     long long sweeps;
@@ -77,6 +82,7 @@ void orc_ctx_init(orc_ctx *c)
     c->sweeps = 0;
     c->early_exits = 0;
     c->smooth_calls = 0;
+    c->last_exits = 0;
 }
 
 int orc_ctx_size(void) { return (int)sizeof(orc_ctx); }
@@ -180,6 +186,7 @@ int orc_jacobi_smooth(orc_ctx *c, real *x, const real *f, int W, int H, double h
         double nr = orc_residual_norm_seq(x, f, W, H, h);
         if (nr < c->eps) {
             c->early_exits++;
+            if (it == num_iter) c->last_exits++;
             break;
         }
     }

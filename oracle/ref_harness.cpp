@@ -6,8 +6,13 @@
 // copied into this repository.  Used to generate tests/golden/ and to pin
 // oracle/pgmg_oracle.c bit for bit.
 //
-// Usage: ref_harness <V|W|F|G> <N> <cycles> <eps> [phi_out.bin]
+// Usage: ref_harness <V|W|F|G> <N> <cycles> <eps> [phi_out.bin|- [alpha [n_coarse]]]
 //   G = FMG start + W-cycles (BASELINE config 5): cycle 1 is an F-cycle, later ones W
+//   alpha    : the W-cycle's recursion count, MultigridSolver's constructor argument
+//              (MultiGrid.hpp:22); absent: 3 (2_part_MG/main.cpp:15)
+//   n_coarse : MultigridSolver::N_coarse (MultiGrid.hpp:19), set before the F-cycle's
+//              coarsest size is read from it; absent: the reference's own 5
+//   phi_out.bin "-": no dump (a placeholder so the two parameters can follow)
 // Prints one line per cycle:
 //   cycle <k> relerr <e> res <r> center <phi[(N/2)*N+N/2]> hash <fnv64> sweeps <s> exits <x>
 //   seconds <wall time of the reference's cycle call alone>  (bench.py's cpu_baseline)
@@ -132,13 +137,20 @@ int main(int argc, char **argv)
 {
     if (argc > 1 && argv[1][0] == 'O') return op_mode(argc, argv);
     if (argc < 5) {
-        std::fprintf(stderr, "usage: %s <V|W|F|G> <N> <cycles> <eps> [phi_out.bin]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s <V|W|F|G> <N> <cycles> <eps> [phi_out.bin|- [alpha [n_coarse]]]\n",
+                     argv[0]);
         return 2;
     }
     const char kind = argv[1][0];
     const int N = std::atoi(argv[2]);
     const int cycles = std::atoi(argv[3]);
     const double eps = std::atof(argv[4]);
+    const int alpha = argc > 6 ? std::atoi(argv[6]) : 3;
+    const int n_coarse = argc > 7 ? std::atoi(argv[7]) : 0;   // 0: the reference's default
+    if (alpha < 1 || (argc > 7 && n_coarse < 3)) {
+        std::fprintf(stderr, "alpha must be >= 1 and n_coarse >= 3\n");
+        return 2;
+    }
     const long long L = (long long)N * N;
     const double h = a / (N - 1);
 
@@ -151,7 +163,8 @@ int main(int argc, char **argv)
     DynamicGridUtils::compute_exact_solution(ex, h, N, N);
 
     CountingJacobi sm(eps);
-    MultigridSolver mg(&sm, 3, N);
+    MultigridSolver mg(&sm, alpha, N);
+    if (n_coarse > 0) mg.N_coarse = n_coarse;
     const int n0 = mg.N_coarse;
     const double h0 = 1.0 / (n0 - 1);
     double *f0 = new double[n0 * n0];
@@ -185,7 +198,7 @@ int main(int argc, char **argv)
                     (unsigned long long)fnv(phi, L), sm.sweeps, sm.exits, secs);
         std::fflush(stdout);
     }
-    if (argc > 5) {
+    if (argc > 5 && std::strcmp(argv[5], "-") != 0) {
         FILE *fp = std::fopen(argv[5], "wb");
         if (!fp) return 3;
         std::fwrite(phi, sizeof(double), (size_t)L, fp);

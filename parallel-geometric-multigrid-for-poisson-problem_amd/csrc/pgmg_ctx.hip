@@ -150,6 +150,19 @@ int pgmg_create(pgmg_ctx **out, const pgmg_config *cfg)
     if (cfg->v1 < 0 || cfg->v2 < 0 || cfg->v1 + 1 >= kMaxSweeps || cfg->v2 + 1 >= kMaxSweeps ||
         cfg->coarse_iter < 0 || cfg->n_coarse < 3 || cfg->alpha < 1)
         return set_err(PGMG_ERR_ARG, "bad smoother/cycle parameters");
+    // the tail's visit counters are 4 bits per level (pgmg_tail.hip, tail_gcycle): with
+    // alpha >= 16 a count wraps to 0 and the W-cycle would never leave the level
+    if (cfg->alpha > 15)
+        return set_err(PGMG_ERR_ARG, "alpha must be at most 15 (include/pgmg.h)");
+    {
+        // the coarsest level (the first N_l <= n_coarse) is the smallest the tail's top level
+        // can be, whatever tail_n says; the tail holds at most kTailMaxN points per side in LDS
+        int Nl = cfg->N;
+        while (Nl > cfg->n_coarse) Nl = (Nl - 1) / 2 + 1;
+        if (Nl > kTailMaxN)
+            return set_err(PGMG_ERR_ARG, "n_coarse too large: the coarsest level must have at "
+                                         "most 65 points per side (include/pgmg.h)");
+    }
     if (cfg->world < 1 || cfg->rank < 0 || cfg->rank >= cfg->world)
         return set_err(PGMG_ERR_ARG, "bad rank/world");
     if (cfg->precision != PGMG_PRECISION_FP64 && cfg->precision != PGMG_PRECISION_FP32)
@@ -617,6 +630,9 @@ static int run_cycles_core(pgmg_ctx *c, int ncycles, int gamma)
     // is never a captured graph, so the smaller grids gain as much)
     const bool w_spec = gamma > 1 && c->fused && c->comm == nullptr &&
                         !(c->cfg.flags & (PGMG_FLAG_NO_SPEC_FIRE | PGMG_FLAG_EXACT_DIST));
+    // pgmg_spec_visit_modes: the counts are this call's (zeros after a V call, also one that
+    // runs in-stream and never reaches run_cycles_spec)
+    c->wcount[0] = c->wcount[1] = c->wcount[2] = 0;
     if (!c->hist.spec_off && (gamma == 1 ? c->spec : w_spec)) return run_cycles_spec(c, ncycles, gamma);
     return run_cycles_plain(c, ncycles, gamma);
 }

@@ -3,7 +3,7 @@
 
 Run in the build container only (needs /root/reference and `make -C oracle ref`):
 
-    python tests/golden/make_golden.py [--big]
+    python tests/golden/make_golden.py [--big] [--params-only]
 
 The reference (2_part_MG/MultiGrid.hpp + Smoother.hpp + DynamicGridUtils.hpp) is compiled
 unmodified by oracle/Makefile into oracle/_ref/ref_harness; this script only runs it and
@@ -11,6 +11,14 @@ stores inputs/outputs as data:
 
   cycles.json        per-cycle relerr / residual norm / centre value / FNV-64 hash of phi /
                      cumulative sweep and early-exit counts, for V, W and F cycles
+  cycles_params.json the same rows for runs with the W-cycle's alpha and the recursion floor
+                     N_coarse off the reference's defaults (PARAM_CASES): ref_harness passes
+                     alpha to MultigridSolver's constructor (MultiGrid.hpp:22) and sets its
+                     public member N_coarse (:19); each case records both.  coarse_iter is
+                     the literal 10 in the reference (:61, :100) and cannot be varied here.
+                     Provenance: every row is stdout of oracle/_ref/ref_harness, i.e. of the
+                     reference's own unmodified MultigridSolver; recorded results, no code.
+                     (--params-only regenerates this file alone, in about a second)
   phi_<K><N>_c<k>.npy  full phi vectors for small N (N <= 129)
   ops_N<N>.npz       seeded random inputs and the reference's residual, restriction,
                      prolongation and smoother outputs (op-level known-answer tests)
@@ -47,6 +55,51 @@ CASES = [
     ("F", 33, 3, 1e-7, [3]),
     ("F", 129, 2, 1e-7, [2]),
     ("F", 1025, 1, 1e-7, []),
+]
+# Off the defaults: (kind, N, cycles, eps, alpha, n_coarse), N <= 257 and at most 4 cycles.
+# eps from {1e-7, 1e-2, 1e-4, 1e3, 0.0}: checks that all fire, none, and a mix.
+PARAM_CASES = [
+    # W-cycles, alpha 1, 2, 4 and 15 (15: the largest the library accepts)
+    ("W", 65, 3, 1e-7, 1, 5),
+    ("W", 65, 3, 1e-7, 2, 5),
+    ("W", 129, 3, 1e-4, 2, 5),
+    ("W", 257, 3, 1e-2, 2, 5),
+    ("W", 65, 3, 1e-7, 4, 5),
+    ("W", 129, 3, 1e-4, 4, 5),
+    ("W", 33, 4, 0.0, 4, 5),
+    ("W", 257, 2, 1e3, 4, 5),
+    ("W", 33, 2, 1e-7, 15, 5),
+    ("W", 17, 2, 1e-2, 15, 5),
+    # V and W with n_coarse 3, 9, 17 (W also combined with alpha)
+    ("V", 65, 4, 1e-7, 3, 3),
+    ("V", 257, 3, 1e3, 3, 3),
+    ("V", 129, 3, 1e-2, 3, 9),
+    ("V", 65, 3, 0.0, 3, 9),
+    ("V", 129, 3, 1e-4, 3, 17),
+    ("V", 257, 3, 1e-7, 3, 17),
+    ("W", 65, 3, 1e-7, 3, 3),
+    ("W", 65, 3, 1e-7, 2, 3),
+    ("W", 129, 2, 0.0, 3, 3),
+    ("W", 129, 3, 1e-4, 3, 9),
+    ("W", 129, 3, 1e-4, 4, 9),
+    ("W", 65, 3, 1e-2, 3, 17),
+    ("W", 129, 3, 1e-7, 4, 17),
+    ("W", 257, 2, 1e3, 2, 17),
+    # a recursion floor that is no grid size (7, 8: the same cycle as 5; 100 at 257: as 65)
+    ("V", 65, 3, 1e-7, 3, 7),
+    ("W", 65, 2, 1e-7, 3, 8),
+    ("V", 257, 2, 1e-7, 3, 100),
+    # the whole tail one coarsest solve; one-level hierarchies larger than 5x5
+    ("V", 129, 4, 1e-7, 3, 65),
+    ("V", 129, 3, 1e-2, 3, 65),
+    ("V", 33, 4, 1e-7, 3, 33),
+    ("V", 33, 3, 1e-4, 3, 100),
+    ("W", 33, 3, 1e3, 2, 33),
+    # F-cycles: the chain starts from an n_coarse x n_coarse grid
+    ("F", 65, 3, 1e-7, 3, 3),
+    ("F", 33, 3, 1e3, 3, 3),
+    ("F", 129, 2, 1e-4, 3, 9),
+    ("F", 129, 2, 0.0, 3, 17),
 ]
 # Full-size cases (python make_golden.py --big: ~45 min on one core, <= 60 GB RSS).
 # (kind, N, cycles, tool): tool "ref" = the compiled reference (oracle/_ref/ref_harness,
@@ -112,6 +165,23 @@ def run_case(kind, N, cycles, eps, dumps, tmp):
     return {"kind": kind, "N": N, "eps": eps, "cycles": rows}
 
 
+def run_param_case(kind, N, cycles, eps, alpha, n_coarse):
+    assert N <= 257 and cycles <= 4
+    out = subprocess.run([str(HARNESS), kind, str(N), str(cycles), repr(eps), "-", str(alpha),
+                          str(n_coarse)], check=True, capture_output=True, text=True).stdout
+    rows = [parse(l) for l in out.splitlines() if l.startswith("cycle")]
+    assert len(rows) == cycles, (kind, N, alpha, n_coarse, len(rows))
+    return {"kind": kind, "N": N, "eps": eps, "alpha": alpha, "n_coarse": n_coarse,
+            "cycles": rows}
+
+
+def write_params():
+    res = [run_param_case(*c) for c in PARAM_CASES]
+    jpath = HERE / "cycles_params.json"
+    jpath.write_text(json.dumps(res, indent=1) + "\n")
+    print(f"wrote {len(res)} cases to {jpath}")
+
+
 def make_ops(N, seed, tmp):
     rng = np.random.default_rng(seed)
     Nc = (N - 1) // 2 + 1
@@ -141,9 +211,14 @@ def main():
     ap.add_argument("--ingest", metavar="DIR",
                     help="with --big: read the BIG cases' stdout from DIR/<kind><N>.txt")
     ap.add_argument("--big-only", action="store_true", help="skip the small cases")
+    ap.add_argument("--params-only", action="store_true",
+                    help="write cycles_params.json only (PARAM_CASES)")
     args = ap.parse_args()
     if not HARNESS.exists():
         raise SystemExit("build the reference harness first: make -C oracle ref")
+    write_params()
+    if args.params_only:
+        return
     prev = []
     jpath = HERE / "cycles.json"
     if jpath.exists():

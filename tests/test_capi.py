@@ -103,6 +103,34 @@ def test_retired_flag_bits_rejected(pgmg, bit):
     assert not h.value
 
 
+@pytest.mark.parametrize("alpha", [16, 17, 64, 2 ** 31 - 1])
+def test_alpha_above_tail_counters_rejected(pgmg, alpha):
+    """alpha > 15 fails pgmg_create with PGMG_ERR_ARG before any device call: the tail counts a
+    level's visits in 4 bits (pgmg_tail.hip, tail_gcycle), so a W-cycle with alpha >= 16 would
+    never leave a tail level.  Nothing else runs here: such a cycle must never be started."""
+    lib = pgmg.load()
+    cfg = pgmg.default_config(33)
+    cfg.alpha = alpha
+    h = C.c_void_p()
+    assert lib.pgmg_create(C.byref(h), C.byref(cfg)) == -1   # PGMG_ERR_ARG
+    assert not h.value
+
+
+@pytest.mark.parametrize("N,n_coarse", [(129, 129), (257, 129), (257, 200), (257, 257),
+                                        (513, 1000), (129, 2 ** 31 - 1)])
+def test_n_coarse_above_tail_limit_rejected(pgmg, N, n_coarse):
+    """A recursion floor that makes the coarsest level (the first N_l <= n_coarse, the tail's
+    top level) larger than 65x65 fails pgmg_create with PGMG_ERR_ARG before any device call:
+    the tail keeps its levels in LDS and holds no more.  (257 with 100, 65 with 1000 and 33 with
+    33 are legal: tests/test_gpu_cycle_params.py runs them.)"""
+    lib = pgmg.load()
+    cfg = pgmg.default_config(N)
+    cfg.n_coarse = n_coarse
+    h = C.c_void_p()
+    assert lib.pgmg_create(C.byref(h), C.byref(cfg)) == -1   # PGMG_ERR_ARG
+    assert not h.value
+
+
 def test_library_built_from_this_tree(pgmg):
     """libpgmg.so carries the hash of the sources it was built from (Makefile "srchash"); it
     must equal this tree's, so the library the GPU box loads is the one these sources make."""

@@ -44,6 +44,51 @@ def test_golden_cycles_hashes(oracle_mod, golden_cycles):
     assert checked > 100
 
 
+def test_golden_cycles_params_hashes(oracle_mod):
+    """The oracle off the defaults: alpha and n_coarse against the reference's own
+    MultigridSolver (tests/golden/cycles_params.json, written by make_golden.py from
+    oracle/_ref/ref_harness with alpha as the constructor argument and N_coarse set).  Every
+    cycle's hash, centre value, sweep and exit counts, residual norm and relative error.
+
+    coarse_iter cannot be pinned this way: the reference fixes it as the literal 10
+    (MultiGrid.hpp:61, :100).  For coarse_iter the oracle's own
+    orc_smooth_alloc(c, ..., c->coarse_iter) at the recursion floor is the definition."""
+    import json
+    cases = json.loads((GOLDEN / "cycles_params.json").read_text())
+    checked = 0
+    seen = set()
+    for case in cases:
+        kind, N, eps = case["kind"], case["N"], case["eps"]
+        alpha, n_coarse = case["alpha"], case["n_coarse"]
+        assert N <= 257 and len(case["cycles"]) <= 4
+        seen.add((kind, alpha, n_coarse))
+        o = oracle_mod.Oracle(eps=eps, alpha=alpha, n_coarse=n_coarse)
+        f = o.rhs(N)
+        phi = np.zeros((N, N))
+        h = 1.0 / (N - 1)
+        for row in case["cycles"]:
+            if kind == "V":
+                o.v_cycle(phi, f)
+            elif kind == "W":
+                o.w_cycle(phi, f)
+            else:
+                o.f_cycle_outer(phi)
+            tag = f"{kind} N={N} eps={eps} alpha={alpha} n_coarse={n_coarse} cycle={row['cycle']}"
+            assert oracle_mod.fnv_hash(phi) == row["hash"], tag
+            assert phi[N // 2, N // 2] == row["center"], tag
+            assert o.sweeps == row["sweeps"], tag
+            assert o.early_exits == row["exits"], tag
+            r = oracle_mod.residual(phi, f, h)
+            assert oracle_mod.norm(r) == row["res"], tag
+            assert o.rel_error(phi) == row["relerr"], tag
+            checked += 1
+    # the fixture covers what it is there for (a regenerated file cannot quietly shrink)
+    assert {a for k, a, _ in seen if k == "W"} >= {1, 2, 4, 15}
+    for kind, floors in (("V", {3, 9, 17, 33, 65, 100}), ("W", {3, 9, 17}), ("F", {3, 9})):
+        assert {n for k, _, n in seen if k == kind} >= floors, kind
+    assert checked >= 90
+
+
 @pytest.mark.parametrize("name", sorted(p.name for p in GOLDEN.glob("phi_*.npy")))
 def test_golden_phi_vectors(oracle_mod, name):
     stem = name[len("phi_"):-len(".npy")]
