@@ -176,7 +176,15 @@ typedef struct pgmg_config {
     int alpha;         /* W-cycle recursion count, default 3; 1 .. 15 (the tail counts a
                           level's visits in 4 bits): pgmg_create returns PGMG_ERR_ARG above */
     double eps;        /* smoother early-exit tolerance, default 1e-7; <0: never */
-    double a, p, q;    /* domain edge and RHS wave numbers, default 1, 1, 1      */
+    double a, p, q;    /* domain edge and RHS wave numbers, default 1, 1, 1: the reference's
+                          globals (globals.cpp:2-4), f = pi^2 / a^2 (p^2 + q^2) u with
+                          u = sin(p pi x / a) sin(q pi y / a).  a: finite and not 0 (a < 0
+                          is legal: h < 0, h^2 > 0); p, q: finite -- negative, zero (f = 0,
+                          then pgmg_monitor's exact_norm is 0 and rel_error is err_norm / 0:
+                          NaN for phi = 0, Inf otherwise, as the reference prints) and
+                          non-integer values (u != 0 on the far boundary, while phi's
+                          boundary stays the caller's) are legal.  pgmg_create returns
+                          PGMG_ERR_ARG for a = 0 and for a non-finite a, p or q           */
     int tail_n;        /* levels with N <= tail_n run in one workgroup (<= 65)   */
     int device;        /* HIP device ordinal, default 0                          */
     unsigned flags;    /* PGMG_FLAG_*                                            */

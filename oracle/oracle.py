@@ -68,6 +68,7 @@ def lib(dtype="f64"):
             "orc_w_cycle": (None, [P, P, P, C.c_int, C.c_double]),
             "orc_f_cycle_outer": (None, [P, P, C.c_int]),
             "orc_rel_error": (C.c_double, [P, P, C.c_int]),
+            "orc_rel_error_h": (C.c_double, [P, P, C.c_int, C.c_double]),
             "orc_residual_norm": (C.c_double, [P, P, C.c_int, C.c_double]),
             "orc_hash": (C.c_uint64, [P, C.c_longlong]),
             "orc_real_size": (C.c_int, []),
@@ -125,9 +126,9 @@ class Oracle:
         self.L.orc_rhs(C.byref(self.c), _p(f), N, N, h)
         return f
 
-    def exact(self, N):
+    def exact(self, N, h=None):
         u = np.zeros((N, N))
-        self.L.orc_exact(C.byref(self.c), _p(u), self.c.a / (N - 1), N, N)
+        self.L.orc_exact(C.byref(self.c), _p(u), self.c.a / (N - 1) if h is None else h, N, N)
         return u
 
     def v_cycle(self, phi, f, h=None):
@@ -153,9 +154,12 @@ class Oracle:
         return self.L.orc_jacobi_smooth(C.byref(self.c), _p(x), _p(f), N, N, h, num_iter,
                                         _p(work))
 
-    def rel_error(self, phi):
+    def rel_error(self, phi, h=None):
+        """h: the mesh width the exact solution is taken at (None: a / (N - 1))."""
         phi = np.ascontiguousarray(phi, dtype=self.dt)
-        return self.L.orc_rel_error(C.byref(self.c), _p(phi), phi.shape[0])
+        if h is None:
+            return self.L.orc_rel_error(C.byref(self.c), _p(phi), phi.shape[0])
+        return self.L.orc_rel_error_h(C.byref(self.c), _p(phi), phi.shape[0], h)
 
     def _chk(self, *arrays):
         for a in arrays:

@@ -392,11 +392,11 @@ void orc_f_cycle_outer(orc_ctx *c, real *phi, int N)
 
 /* ---- harness helpers ---------------------------------------------------- */
 
-/* ||phi - u|| / ||u|| as printed by MultiGridTestRunner.hpp:252-255 */
-double orc_rel_error(const orc_ctx *c, const real *phi, int N)
+/* ||phi - u|| / ||u|| as printed by MultiGridTestRunner.hpp:252-255, the exact solution taken
+ * at the caller's mesh width h (compute_exact_solution's argument) */
+double orc_rel_error_h(const orc_ctx *c, const real *phi, int N, double h)
 {
     /* sequential sums in fp64 over the exact solution of orc_exact (fp32: phi widened) */
-    double h = c->a / (N - 1);
     double se = 0.0, su = 0.0;
     for (int j = 0; j < N; ++j) {
         for (int i = 0; i < N; ++i) {
@@ -409,6 +409,12 @@ double orc_rel_error(const orc_ctx *c, const real *phi, int N)
         }
     }
     return sqrt(se) / sqrt(su);
+}
+
+/* the same at h = a / (N - 1) (MultiGridTestRunner.hpp:131) */
+double orc_rel_error(const orc_ctx *c, const real *phi, int N)
+{
+    return orc_rel_error_h(c, phi, N, c->a / (N - 1));
 }
 
 /* sqrt(sum_interior r^2) of the current iterate */

@@ -6,13 +6,18 @@
 // copied into this repository.  Used to generate tests/golden/ and to pin
 // oracle/pgmg_oracle.c bit for bit.
 //
-// Usage: ref_harness <V|W|F|G> <N> <cycles> <eps> [phi_out.bin|- [alpha [n_coarse]]]
+// Usage: ref_harness <V|W|F|G> <N> <cycles> <eps> [phi_out.bin|- [alpha [n_coarse [a p q [h]]]]]
 //   G = FMG start + W-cycles (BASELINE config 5): cycle 1 is an F-cycle, later ones W
 //   alpha    : the W-cycle's recursion count, MultigridSolver's constructor argument
 //              (MultiGrid.hpp:22); absent: 3 (2_part_MG/main.cpp:15)
 //   n_coarse : MultigridSolver::N_coarse (MultiGrid.hpp:19), set before the F-cycle's
 //              coarsest size is read from it; absent: the reference's own 5
-//   phi_out.bin "-": no dump (a placeholder so the two parameters can follow)
+//   a p q    : the reference's problem constants, its globals a, p, q (globals.cpp:2-4), assigned
+//              before anything reads them; absent: the reference's own 1, 1, 1
+//   h        : the mesh width handed to compute_rhs, compute_exact_solution, v_cycle / w_cycle
+//              (the h argument of MultiGrid.hpp:57) and compute_residual; "-" or absent:
+//              a / (N - 1).  The F-cycle keeps its own chain from 1 / (n_coarse - 1).
+//   phi_out.bin "-": no dump (a placeholder so the parameters can follow)
 // Prints one line per cycle:
 //   cycle <k> relerr <e> res <r> center <phi[(N/2)*N+N/2]> hash <fnv64> sweeps <s> exits <x>
 //   seconds <wall time of the reference's cycle call alone>  (bench.py's cpu_baseline)
@@ -137,8 +142,8 @@ int main(int argc, char **argv)
 {
     if (argc > 1 && argv[1][0] == 'O') return op_mode(argc, argv);
     if (argc < 5) {
-        std::fprintf(stderr, "usage: %s <V|W|F|G> <N> <cycles> <eps> [phi_out.bin|- [alpha [n_coarse]]]\n",
-                     argv[0]);
+        std::fprintf(stderr, "usage: %s <V|W|F|G> <N> <cycles> <eps> [phi_out.bin|- [alpha [n_coarse "
+                             "[a p q [h]]]]]\n", argv[0]);
         return 2;
     }
     const char kind = argv[1][0];
@@ -151,8 +156,17 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "alpha must be >= 1 and n_coarse >= 3\n");
         return 2;
     }
+    if (argc > 8 && argc < 11) {
+        std::fprintf(stderr, "a, p and q come together\n");
+        return 2;
+    }
+    if (argc > 10) {
+        a = std::atof(argv[8]);
+        p = std::atof(argv[9]);
+        q = std::atof(argv[10]);
+    }
     const long long L = (long long)N * N;
-    const double h = a / (N - 1);
+    const double h = argc > 11 && std::strcmp(argv[11], "-") != 0 ? std::atof(argv[11]) : a / (N - 1);
 
     double *phi = new double[L];
     double *f = new double[L];

@@ -169,6 +169,12 @@ int pgmg_create(pgmg_ctx **out, const pgmg_config *cfg)
         return set_err(PGMG_ERR_ARG, "precision must be PGMG_PRECISION_FP64 or _FP32");
     if (!(cfg->h0 >= 0.0) || !std::isfinite(cfg->h0))
         return set_err(PGMG_ERR_ARG, "h0 must be finite and >= 0 (0: a / (N - 1))");
+    // a divides in every sine table and in the right-hand side's factor: a = 0 or a non-finite
+    // a, p or q makes them NaN / Inf, and with them every result of the context
+    if (!std::isfinite(cfg->a) || cfg->a == 0.0)
+        return set_err(PGMG_ERR_ARG, "a must be finite and not 0 (include/pgmg.h)");
+    if (!std::isfinite(cfg->p) || !std::isfinite(cfg->q))
+        return set_err(PGMG_ERR_ARG, "p and q must be finite (include/pgmg.h)");
     if (cfg->flags & PGMG_FLAGS_RETIRED)
         return set_err(PGMG_ERR_ARG, "retired PGMG_FLAG_* bit (8192 / 16384; include/pgmg.h): "
                                      "PGMG_FLAG_NO_SPEC_FIRE is 32768 since r04");

@@ -3,7 +3,7 @@
 
 Run in the build container only (needs /root/reference and `make -C oracle ref`):
 
-    python tests/golden/make_golden.py [--big] [--params-only]
+    python tests/golden/make_golden.py [--big] [--params-only] [--problem-only]
 
 The reference (2_part_MG/MultiGrid.hpp + Smoother.hpp + DynamicGridUtils.hpp) is compiled
 unmodified by oracle/Makefile into oracle/_ref/ref_harness; this script only runs it and
@@ -19,12 +19,21 @@ stores inputs/outputs as data:
                      Provenance: every row is stdout of oracle/_ref/ref_harness, i.e. of the
                      reference's own unmodified MultigridSolver; recorded results, no code.
                      (--params-only regenerates this file alone, in about a second)
+  cycles_problem.json the same rows with the problem's constants off the reference's defaults
+                     (PROBLEM_CASES): ref_harness assigns the reference's globals a, p, q
+                     (globals.cpp:2-4) before anything reads them and, for V and W, hands the
+                     case's mesh width h to compute_rhs, compute_exact_solution, v_cycle /
+                     w_cycle and compute_residual; each case records a, p, q and h (null:
+                     a / (N - 1)).  A relerr that is not finite (p = 0: the exact solution is
+                     0 everywhere) is stored as null.  Recorded results of the reference's own
+                     unmodified code, as above.  (--problem-only regenerates this file alone)
   phi_<K><N>_c<k>.npy  full phi vectors for small N (N <= 129)
   ops_N<N>.npz       seeded random inputs and the reference's residual, restriction,
                      prolongation and smoother outputs (op-level known-answer tests)
 """
 import argparse
 import json
+import math
 import os
 import pathlib
 import subprocess
@@ -101,6 +110,55 @@ PARAM_CASES = [
     ("F", 129, 2, 1e-4, 3, 9),
     ("F", 129, 2, 0.0, 3, 17),
 ]
+# The problem's constants off the defaults: (kind, N, cycles, eps, a, p, q, h), N <= 129 and at
+# most 3 cycles.  h None: a / (N - 1); "H1": 0.7 / (N - 1); "H2": 1 / N (V and W only: the
+# F-cycle runs its own chain).  The sets P1 .. P10 (p = N - 2 in P8) and a = -2, each with V, W
+# and F; sizes and eps from {1e-7, 1e-2, 1e-4} mixed by position.
+PROBLEM_SETS = [
+    ("P1", 1.0, 2.0, 3.0),        # asymmetric
+    ("P2", 2.0, 1.0, 1.0),        # dyadic a != 1
+    ("P3", 3.0, 2.0, 1.0),        # non-dyadic a: i * h rounds
+    ("P4", 0.5, 3.0, 5.0),        # a < 1, higher modes
+    ("P5", 1.0, 0.5, 1.5),        # non-integer: f and u are O(1) on column and row N - 1
+    ("P6", 1.0, -1.0, 2.0),       # negative wave number
+    ("P7", 1.0, 0.0, 1.0),        # f = 0
+    ("P8", 1.0, None, 1.0),       # p = N - 2: the mode one undamped Jacobi sweep annihilates
+    ("P9", 1000.0, 2.0, 2.0),     # f ~ 1e-5
+    ("P10", 1e-3, 1.0, 1.0),      # f ~ 2e7
+    ("neg", -2.0, 1.0, 2.0),      # h < 0, h * h > 0
+]
+
+
+def mesh_width(tag, N):
+    return {None: None, "H1": 0.7 / (N - 1), "H2": 1.0 / N}[tag]
+
+
+def _problem_cases():
+    cases, i = [], 0
+    for kind in ("V", "W", "F"):
+        for _, a, p, q in PROBLEM_SETS:
+            N = (33, 65, 129)[i % 3]
+            eps = (1e-7, 1e-2, 1e-4)[(i // 3 + i) % 3]
+            cases.append((kind, N, 3, eps, a, float(N - 2) if p is None else p, q, None))
+            i += 1
+    # the exit mixes tests/test_gpu_problem_params.py relies on, at N = 65 (its precision split,
+    # V at N = 65 with p = 63, eps 1e-7, is the loop's P8 row for V)
+    for kind, eps, a, p, q in (("V", 1e-7, 1.0, 2.0, 3.0), ("V", 1e-7, 0.5, 3.0, 5.0),
+                               ("V", 1e-2, 1000.0, 2.0, 2.0)):
+        cases.append((kind, 65, 3, eps, a, p, q, None))
+    # the caller's mesh width, with the default problem, P1 and P5
+    for kind in ("V", "W"):
+        for tag in ("H1", "H2"):
+            for j, (a, p, q) in enumerate(((1.0, 1.0, 1.0), (1.0, 2.0, 3.0), (1.0, 0.5, 1.5))):
+                N = (65, 129, 33)[j]
+                eps = (1e-7, 1e-4, 1e-2)[j]
+                cases.append((kind, N, 3, eps, a, p, q, tag))
+    cases.append(("V", 65, 3, 1e-7, 1.0, 1.0, 1.0, 1.0))     # h = 1: every check fires
+    return cases
+
+
+PROBLEM_CASES = _problem_cases()
+
 # Full-size cases (python make_golden.py --big: ~45 min on one core, <= 60 GB RSS).
 # (kind, N, cycles, tool): tool "ref" = the compiled reference (oracle/_ref/ref_harness,
 # whose leak reclaimer keeps its RSS at ~9 grids); "port" = oracle/mg_cpu_exec_port, our C
@@ -182,6 +240,28 @@ def write_params():
     print(f"wrote {len(res)} cases to {jpath}")
 
 
+def run_problem_case(kind, N, cycles, eps, a, p, q, h):
+    assert N <= 129 and cycles <= 3 and kind in "VWF"
+    hv = mesh_width(h, N) if h is None or isinstance(h, str) else h
+    assert hv is None or kind != "F", "the F-cycle runs its own chain of mesh widths"
+    out = subprocess.run([str(HARNESS), kind, str(N), str(cycles), repr(eps), "-", "3", "5",
+                          repr(a), repr(p), repr(q), "-" if hv is None else repr(hv)],
+                         check=True, capture_output=True, text=True).stdout
+    rows = [parse(l) for l in out.splitlines() if l.startswith("cycle")]
+    assert len(rows) == cycles, (kind, N, a, p, q, h, len(rows))
+    for r in rows:
+        if not math.isfinite(r["relerr"]):
+            r["relerr"] = None
+    return {"kind": kind, "N": N, "eps": eps, "a": a, "p": p, "q": q, "h": hv, "cycles": rows}
+
+
+def write_problem():
+    res = [run_problem_case(*c) for c in PROBLEM_CASES]
+    jpath = HERE / "cycles_problem.json"
+    jpath.write_text(json.dumps(res, indent=1, allow_nan=False) + "\n")
+    print(f"wrote {len(res)} cases to {jpath}")
+
+
 def make_ops(N, seed, tmp):
     rng = np.random.default_rng(seed)
     Nc = (N - 1) // 2 + 1
@@ -213,9 +293,15 @@ def main():
     ap.add_argument("--big-only", action="store_true", help="skip the small cases")
     ap.add_argument("--params-only", action="store_true",
                     help="write cycles_params.json only (PARAM_CASES)")
+    ap.add_argument("--problem-only", action="store_true",
+                    help="write cycles_problem.json only (PROBLEM_CASES)")
     args = ap.parse_args()
     if not HARNESS.exists():
         raise SystemExit("build the reference harness first: make -C oracle ref")
+    if not args.params_only:
+        write_problem()
+    if args.problem_only:
+        return
     write_params()
     if args.params_only:
         return

@@ -131,6 +131,25 @@ def test_n_coarse_above_tail_limit_rejected(pgmg, N, n_coarse):
     assert not h.value
 
 
+@pytest.mark.parametrize("field,value", [("a", 0.0), ("a", -0.0), ("a", float("nan")),
+                                         ("a", float("inf")), ("a", float("-inf")),
+                                         ("p", float("nan")), ("p", float("inf")),
+                                         ("q", float("nan")), ("q", float("-inf"))])
+def test_unrunnable_problem_constants_rejected(pgmg, field, value):
+    """a = 0 or a non-finite a, p or q fails pgmg_create with PGMG_ERR_ARG and a message before
+    any device call: a divides in every sine table and in the right-hand side's factor, so
+    such a context's every result would be NaN.  (Negative a and negative, zero or non-integer
+    p and q are legal: tests/test_gpu_problem_params.py runs them.)"""
+    lib = pgmg.load()
+    cfg = pgmg.default_config(33)
+    setattr(cfg, field, value)
+    h = C.c_void_p()
+    assert lib.pgmg_create(C.byref(h), C.byref(cfg)) == -1   # PGMG_ERR_ARG
+    assert not h.value
+    msg = lib.pgmg_last_error().decode()
+    assert ("p and q" if field in "pq" else "a must") in msg, msg
+
+
 def test_library_built_from_this_tree(pgmg):
     """libpgmg.so carries the hash of the sources it was built from (Makefile "srchash"); it
     must equal this tree's, so the library the GPU box loads is the one these sources make."""

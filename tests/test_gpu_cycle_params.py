@@ -35,20 +35,24 @@ from test_gpu_strips import _run_ranks, _single
 
 gpu = pytest.mark.gpu
 
-ORACLE_KEYS = ("alpha", "n_coarse", "coarse_iter", "v1", "v2")
+# pgmg_config fields that the oracle takes too; h0 (tests/test_gpu_problem_params.py) is the
+# mesh width handed to the oracle's rhs and cycle calls, 0 or absent: a / (N - 1)
+ORACLE_KEYS = ("alpha", "n_coarse", "coarse_iter", "v1", "v2", "a", "p", "q", "h0")
 EPS5 = [1e-7, 1e-2, 1e-4, 1e3, 0.0]
 
 
 def _problem(N, dtype, rand):
     """(phi0, f) as float64 arrays holding values of `dtype`; (None, None): phi0 = 0 and the
     analytic f.  rand: a random phi0 with a non-zero boundary and the mt19937_64 robustness
-    right-hand side."""
+    right-hand side; rand = "phi": that phi0 with the analytic f."""
     if not rand:
         return None, None
     dt = np.float32 if dtype == "f32" else np.float64
     rng = np.random.default_rng(4242 + N)
     phi0 = rng.uniform(-1.0, 1.0, (N, N)).astype(dt).astype(np.float64)
     assert np.abs(phi0[0]).min() > 0 and np.abs(phi0[:, -1]).min() > 0
+    if rand == "phi":
+        return phi0, None
     f = oracle.rhs_mt64(N, dtype=dtype).astype(np.float64)
     return phi0, f
 
@@ -59,9 +63,10 @@ def _reference(kind, N, cycles, dtype, eps, rand, okw):
     every cycle], (early_exits, smooth_calls) at the end).  A W-cycle with alpha = 1 is
     o.v_cycle."""
     kw = dict(okw)
+    h = kw.pop("h0", 0.0) or None
     o = oracle.Oracle(eps=eps, dtype=dtype, **kw)
     phi0, f = _problem(N, dtype, rand)
-    f = o.rhs(N) if f is None else np.ascontiguousarray(f, dtype=o.dt)
+    f = o.rhs(N, h) if f is None else np.ascontiguousarray(f, dtype=o.dt)
     phi = np.zeros((N, N), dtype=o.dt) if phi0 is None else np.array(phi0, dtype=o.dt)
     step = {"V": o.v_cycle, "W": o.v_cycle if kw.get("alpha", 3) == 1 else o.w_cycle}.get(kind)
     snaps = []
@@ -69,7 +74,7 @@ def _reference(kind, N, cycles, dtype, eps, rand, okw):
         if kind == "F":
             o.f_cycle_outer(phi)
         else:
-            step(phi, f)
+            step(phi, f, h)
         snap = phi.astype(np.float64)
         snap.setflags(write=False)
         snaps.append((snap, o.sweeps, o.cut_exits))

@@ -16,7 +16,21 @@ from conftest import assert_bitwise
 pytestmark = pytest.mark.gpu
 
 
-def _run_ranks(pgmg, world, N, cycles, kind="V", **cfg):
+def _cycles(s, cycles, kind, calls, monitor):
+    """`cycles` one-cycle calls of `kind` ("V" / "W"), or the calls given as (kind, n) pairs with
+    kind "V", "W" or "F"; (phi, stats, residual norm), and with monitor also pgmg_monitor's four
+    norms with the error sums and whether the calls were speculative."""
+    run = {"V": s.vcycle, "W": s.wcycle, "F": s.fcycle}
+    for k, n in [(kind, 1)] * cycles if calls is None else calls:
+        run[k](n)
+    out = (s.solution(), s.stats(), s.residual_norm())
+    if monitor:
+        m = s.monitor(error=True)
+        out += ((m.res_norm, m.err_norm, m.exact_norm, m.rel_error), s.dist_info()[0])
+    return out
+
+
+def _run_ranks(pgmg, world, N, cycles, kind="V", calls=None, monitor=False, **cfg):
     hub = pgmg.LoopbackHub(world)
     out = [None] * world
     err = [None] * world
@@ -25,18 +39,18 @@ def _run_ranks(pgmg, world, N, cycles, kind="V", **cfg):
         try:
             with pgmg.Solver(N, hub=hub, rank=r, **cfg) as s:
                 s.set_problem(*_problem.get(r, (None, None)))
-                for _ in range(cycles):
-                    (s.vcycle if kind == "V" else s.wcycle)(1)
-                out[r] = (s.solution(), s.stats(), s.residual_norm())
+                out[r] = _cycles(s, cycles, kind, calls, monitor)
         except Exception as e:  # surfaced below
             err[r] = e
 
     _problem = cfg.pop("problem", {})
-    ts = [threading.Thread(target=work, args=(r,)) for r in range(world)]
+    ts = [threading.Thread(target=work, args=(r,), daemon=True) for r in range(world)]
     for t in ts:
         t.start()
     for t in ts:
         t.join(timeout=600)
+    hung = [r for r, t in enumerate(ts) if t.is_alive()]
+    assert not hung, f"ranks {hung} of {world} did not finish"
     hub.close()
     for e in err:
         if e is not None:
@@ -44,12 +58,10 @@ def _run_ranks(pgmg, world, N, cycles, kind="V", **cfg):
     return out
 
 
-def _single(pgmg, N, cycles, kind="V", problem=(None, None), **cfg):
+def _single(pgmg, N, cycles, kind="V", problem=(None, None), calls=None, monitor=False, **cfg):
     with pgmg.Solver(N, **cfg) as s:
         s.set_problem(*problem)
-        for _ in range(cycles):
-            (s.vcycle if kind == "V" else s.wcycle)(1)
-        return s.solution(), s.stats(), s.residual_norm()
+        return _cycles(s, cycles, kind, calls, monitor)
 
 
 @pytest.mark.parametrize("world,N,gather_n", [(2, 1025, 65), (4, 1025, 65), (2, 2049, 257),

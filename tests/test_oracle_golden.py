@@ -89,6 +89,68 @@ def test_golden_cycles_params_hashes(oracle_mod):
     assert checked >= 90
 
 
+def test_golden_cycles_problem_hashes(oracle_mod):
+    """The oracle with the problem's constants off the defaults: a, p, q (the reference's
+    globals, globals.cpp:2-4) and, for V and W, the caller's mesh width h (MultiGrid.hpp:57's
+    argument, also compute_rhs's, compute_exact_solution's and compute_residual's) against the
+    reference's own code (tests/golden/cycles_problem.json, written by make_golden.py from
+    oracle/_ref/ref_harness).  Every cycle's hash, centre value, sweep and exit counts,
+    residual norm and relative error.  A relerr of null is the reference's NaN: p = 0, where
+    the exact solution is 0 everywhere and ||e|| / ||u|| is 0 / 0."""
+    import json
+    import math
+    cases = json.loads((GOLDEN / "cycles_problem.json").read_text())
+    checked = 0
+    seen, hs = set(), set()
+    for case in cases:
+        kind, N, eps = case["kind"], case["N"], case["eps"]
+        a, p, q, h = case["a"], case["p"], case["q"], case["h"]
+        assert N <= 129 and len(case["cycles"]) <= 3
+        assert h is None or kind != "F"
+        seen.add((kind, a, p, q))
+        if h is not None:
+            hs.add((kind, "H1" if h == 0.7 / (N - 1) else "H2" if h == 1.0 / N else h))
+        o = oracle_mod.Oracle(eps=eps, a=a, p=p, q=q)
+        hh = a / (N - 1) if h is None else h
+        f = o.rhs(N, hh)
+        phi = np.zeros((N, N))
+        for row in case["cycles"]:
+            if kind == "V":
+                o.v_cycle(phi, f, hh)
+            elif kind == "W":
+                o.w_cycle(phi, f, hh)
+            else:
+                o.f_cycle_outer(phi)
+            tag = f"{kind} N={N} eps={eps} a={a} p={p} q={q} h={h} cycle={row['cycle']}"
+            assert oracle_mod.fnv_hash(phi) == row["hash"], tag
+            assert phi[N // 2, N // 2] == row["center"], tag
+            assert o.sweeps == row["sweeps"], tag
+            assert o.early_exits == row["exits"], tag
+            r = oracle_mod.residual(phi, f, hh)
+            assert oracle_mod.norm(r) == row["res"], tag
+            if row["relerr"] is None:
+                assert p == 0 and math.isnan(o.rel_error(phi, hh)), tag
+            else:
+                assert o.rel_error(phi, hh) == row["relerr"], tag
+                if h is None:   # the entry without h is the same at a / (N - 1)
+                    assert o.rel_error(phi) == row["relerr"], tag
+            checked += 1
+    # the fixture covers what it is there for (a regenerated file cannot quietly shrink)
+    sets = {(1.0, 2.0, 3.0), (2.0, 1.0, 1.0), (3.0, 2.0, 1.0), (0.5, 3.0, 5.0), (1.0, 0.5, 1.5),
+            (1.0, -1.0, 2.0), (1.0, 0.0, 1.0), (1000.0, 2.0, 2.0), (1e-3, 1.0, 1.0),
+            (-2.0, 1.0, 2.0)}
+    for kind in "VWF":
+        mine = {(a, p, q) for k, a, p, q in seen if k == kind}
+        assert mine >= sets, (kind, sets - mine)
+        assert any(p >= 31 and q == 1 for a, p, q in mine), kind          # P8: p = N - 2
+        assert any(math.log2(abs(a)) % 1 for a, p, q in mine), kind       # a non-dyadic a
+        assert any(p % 1 for a, p, q in mine), kind                       # a non-integer p
+        assert any(p != q for a, p, q in mine), kind
+    for kind in "VW":
+        assert {t for k, t in hs if k == kind} >= {"H1", "H2"}, kind
+    assert checked >= 140
+
+
 @pytest.mark.parametrize("name", sorted(p.name for p in GOLDEN.glob("phi_*.npy")))
 def test_golden_phi_vectors(oracle_mod, name):
     stem = name[len("phi_"):-len(".npy")]
