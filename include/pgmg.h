@@ -270,7 +270,8 @@ int pgmg_pointer_is_device(const void *p, int *is_device);
  * pgmg_residual_norm, pgmg_monitor, pgmg_history, pgmg_stats*, pgmg_sync ...) keep the carry
  * (pgmg_solve's checks between its one-cycle calls too); every entry that changes phi,
  * f, eps, the flags or the cycle kind (pgmg_set_problem*, pgmg_set_eps, pgmg_wcycle,
- * pgmg_fcycle, pgmg_bench_sweep, pgmg_phi_device -- its pointer allows writes -- ) drops it.
+ * pgmg_fcycle, pgmg_fmg, pgmg_damp, pgmg_bench_sweep, pgmg_phi_device -- its pointer allows
+ * writes -- ) drops it.
  * A carried pre-smooth whose early-exit check could fire is dropped, not rolled back.  Results
  * and statistics (its two sweeps count in the call that uses them) equal the uncarried ones,
  * bit for bit.  PGMG_FLAG_NO_CARRY turns it off; pgmg_carry_info counts it. */
@@ -369,6 +370,50 @@ int pgmg_solve(pgmg_ctx *ctx, const pgmg_solve_opts *o, pgmg_solve_info *info);
  * in cycle[] (cycles run before the check), res[] and rel_error[] (NaN when not monitored); any
  * of the arrays may be NULL. */
 int pgmg_history(pgmg_ctx *ctx, int cap, int *cycle, double *res, double *rel_error, int *n);
+
+/* ---- Damping pass and damped solve ------------------------------------------------------
+ * The cycles' smoother is the reference's undamped Jacobi: its iteration matrix has the
+ * eigenvalues lambda = (cos tx + cos ty) / 2, and the most oscillatory error (lambda ~ -1, the
+ * checkerboard) passes through v1 + v2 sweeps and every coarse grid unchanged.  A right-hand side
+ * that holds it (any but the smooth analytic one) stalls plain cycles at a factor of 0.94-0.96.
+ *
+ * pgmg_damp: ONE finest-level damped-Jacobi correction of the current iterate,
+ *     phi <- phi + w * r,   r = f - ih (4x - x_l - x_r - x_u - x_d)   (pgmg_monitor's r),
+ *     w = (T)(omega * 0.25 * (h0 * h0))   the double product taken left to right, then converted,
+ * on every interior point, in the context's element type T with two roundings (no fused
+ * multiply-add); boundary points are never written.  Every r is formed from the phi of before
+ * the pass: the result is exactly the out-of-place formula, whatever the launch geometry.  It is
+ * the monitor's pass (same reads, same decomposition, same partial sums) that also writes: with
+ * res_norm != NULL it returns the residual norm of phi BEFORE the update, bit for bit what
+ * pgmg_monitor(PGMG_MON_RESIDUAL) returns on that state.  At omega = 1/2 the factor on an error
+ * mode is (1 + lambda) / 2: 0 on the checkerboard, ~1 on the smooth modes the cycle handles.
+ * Context-owned grids and the caller's arrays of pgmg_set_problem_device (read as the monitor
+ * reads them, written back as double) alike; fp64 and fp32.  Synchronous, like pgmg_monitor.  It
+ * is an entry that changes phi: it drops the carry.  It keeps the speculation history
+ * (validation and rollback protect the results either way) and leaves the sweep and early-exit
+ * statistics untouched.
+ *
+ * pgmg_solve_damped: pgmg_solve's loop and stop rule with every check made by the damping pass.
+ * At check i the pass yields r_i, the norm of the iterate as the cycles left it, and applies the
+ * correction; then the rule decides; then the next chunk of cycles runs.  The correction of the
+ * stopping check is applied too (the pass cannot know the decision), so phi afterwards is
+ * damp(x_k), x_k the iterate info.res was measured on.  For 0 < omega <= 1 the update multiplies
+ * the residual by I - omega (h^2/4) A, a symmetric matrix with its spectrum inside (-1, 1): in
+ * exact arithmetic the returned phi's residual norm is <= info.res (observed 0.80-0.86 x at
+ * omega = 1/2).  pgmg_history records the r_i; with PGMG_MON_ERROR rel_error is that of the
+ * pre-update iterate (the same pass sums it).  Chunks after a damp start uncarried.
+ *
+ * pgmg_damp_time: `reps` damping passes (the pass, the scatter of its deferred edges and the
+ * reduction each) back to back between two hipEvents, after two warm ones; mean device ms per
+ * pass and its algorithmic bytes (the monitor's model + one element per interior point
+ * written).  Leaves phi changed.
+ *
+ * omega not finite, <= 0 or > 1, a null ctx / opts / info, invalid opts: PGMG_ERR_ARG.  Before
+ * pgmg_set_problem*: PGMG_ERR_STATE.  world > 1: PGMG_ERR_STATE -- one GPU only, as pgmg_fmg.
+ * PGMG_MON_ERROR with a caller's f: PGMG_ERR_STATE.  All before anything is enqueued. */
+int pgmg_damp(pgmg_ctx *ctx, double omega, double *res_norm);
+int pgmg_solve_damped(pgmg_ctx *ctx, const pgmg_solve_opts *o, double omega, pgmg_solve_info *info);
+int pgmg_damp_time(pgmg_ctx *ctx, double omega, int reps, double *ms_per_pass, double *bytes);
 
 /* ---- Full multigrid for the problem's own right-hand side -------------------------------
  * pgmg_fcycle is the reference's F-cycle: it rebuilds the ANALYTIC right-hand side on every

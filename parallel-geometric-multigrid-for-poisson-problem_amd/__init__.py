@@ -300,11 +300,31 @@ class Solver:
               "pgmg_monitor_time")
         return ms.value, b.value
 
+    def damp(self, omega=0.5):
+        """One finest-level damped-Jacobi correction phi <- phi + omega (h^2/4) r (pgmg_damp):
+        the monitor's pass that also writes.  Returns the residual norm of phi BEFORE the
+        update.  omega = 1/2 removes the checkerboard error the cycles' undamped smoother
+        leaves.  Drops the carry; one GPU only."""
+        v = C.c_double()
+        check(self.lib.pgmg_damp(self.h, float(omega), C.byref(v)), "pgmg_damp")
+        return v.value
+
+    def damp_time(self, omega=0.5, reps=20):
+        """(mean device ms, algorithmic bytes) of one damping pass over `reps` back to back
+        (pgmg_damp_time; measurement, leaves phi changed)."""
+        ms, b = C.c_double(), C.c_double()
+        check(self.lib.pgmg_damp_time(self.h, float(omega), int(reps), C.byref(ms), C.byref(b)),
+              "pgmg_damp_time")
+        return ms.value, b.value
+
     def solve(self, cycle="V", rtol=1e-3, atol=0.0, max_cycles=30, check_every=1,
-              stall_ratio=0.0, stall_checks=2, error=False):
+              stall_ratio=0.0, stall_checks=2, error=False, damp=0.0):
         """Cycle until the residual norm is at most max(atol, rtol * r0), the cycle cap, a
         stall or a non-finite norm (pgmg_solve; the stop rule: include/pgmg.h).  Returns the
-        PgmgSolveInfo with a `.history` list of (cycle, res, rel_error), check 0 first."""
+        PgmgSolveInfo with a `.history` list of (cycle, res, rel_error), check 0 first.
+        damp: 0.0 is pgmg_solve exactly; a positive omega (0.5 recommended) makes every check a
+        damping pass (pgmg_solve_damped), which converges for any right-hand side; phi afterwards
+        is the damped last iterate, its residual norm at most info.res."""
         o = PgmgSolveOpts()
         check(self.lib.pgmg_solve_opts_default(C.byref(o)), "pgmg_solve_opts_default")
         kinds = {"V": PGMG_CYCLE_V, "W": PGMG_CYCLE_W, "F": PGMG_CYCLE_F}
@@ -313,7 +333,11 @@ class Solver:
         o.stall_ratio, o.stall_checks = stall_ratio, int(stall_checks)
         o.monitor = PGMG_MON_RESIDUAL | (PGMG_MON_ERROR if error else 0)
         info = PgmgSolveInfo()
-        check(self.lib.pgmg_solve(self.h, C.byref(o), C.byref(info)), "pgmg_solve")
+        if damp == 0.0:
+            check(self.lib.pgmg_solve(self.h, C.byref(o), C.byref(info)), "pgmg_solve")
+        else:
+            check(self.lib.pgmg_solve_damped(self.h, C.byref(o), float(damp), C.byref(info)),
+                  "pgmg_solve_damped")
         info.history = self.history()
         return info
 

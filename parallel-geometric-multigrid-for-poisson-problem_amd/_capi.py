@@ -141,6 +141,10 @@ SIGNATURES = [
     ("pgmg_solve_opts_default", C.c_int, [C.POINTER(PgmgSolveOpts)]),
     ("pgmg_solve", C.c_int, [_P, C.POINTER(PgmgSolveOpts), C.POINTER(PgmgSolveInfo)]),
     ("pgmg_history", C.c_int, [_P, C.c_int, C.POINTER(C.c_int), _DP, _DP, C.POINTER(C.c_int)]),
+    ("pgmg_damp", C.c_int, [_P, C.c_double, _DP]),
+    ("pgmg_solve_damped", C.c_int, [_P, C.POINTER(PgmgSolveOpts), C.c_double,
+                                    C.POINTER(PgmgSolveInfo)]),
+    ("pgmg_damp_time", C.c_int, [_P, C.c_double, C.c_int, _DP, _DP]),
     ("pgmg_fmg", C.c_int, [_P, C.c_int]),
     ("pgmg_fmg_interp_time", C.c_int, [_P, C.c_int, _DP, _DP]),
     ("pgmg_stats", C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),

@@ -231,6 +231,10 @@ struct pgmg_ctx {
     const double *mon_sx = nullptr, *mon_sy = nullptr;
     double *mon_buf = nullptr;
     int mon_cap = 0;              // workgroups mon_buf holds partials for
+    // the damping pass (pgmg_damp): its deferred band-edge rows and tile-edge columns, in the
+    // context's element type (allocated on the first call)
+    void *mon_side = nullptr;
+    size_t mon_side_bytes = 0;
     struct SolveRecord {
         int cycle;
         double res, rel_error;

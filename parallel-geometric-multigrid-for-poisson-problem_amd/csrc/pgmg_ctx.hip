@@ -111,6 +111,7 @@ int pgmg_destroy(pgmg_ctx *c)
     if (c->rhs_tab) (void)hipFree(c->rhs_tab);
     if (c->mon_tab) (void)hipFree(c->mon_tab);
     if (c->mon_buf) (void)hipFree(c->mon_buf);
+    if (c->mon_side) (void)hipFree(c->mon_side);
     if (c->fmg_gtab) (void)hipFree(c->fmg_gtab);
     if (c->uflags) (void)hipFree(c->uflags);
     if (c->pin) (void)hipHostFree(c->pin);

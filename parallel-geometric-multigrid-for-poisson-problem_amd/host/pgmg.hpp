@@ -117,6 +117,20 @@ class Context {
         check(pgmg_solve(c_, &o, &info), "pgmg_solve");
         return info;
     }
+    // one damped-Jacobi correction phi += omega (h^2/4) r; the residual norm of before it
+    double damp(double omega = 0.5) const
+    {
+        double r = 0.0;
+        check(pgmg_damp(c_, omega, &r), "pgmg_damp");
+        return r;
+    }
+    // solve() with every check made by the damping pass: converges for any right-hand side
+    pgmg_solve_info solve_damped(const pgmg_solve_opts &o, double omega = 0.5) const
+    {
+        pgmg_solve_info info{};
+        check(pgmg_solve_damped(c_, &o, omega, &info), "pgmg_solve_damped");
+        return info;
+    }
 
   private:
     pgmg_ctx *c_ = nullptr;
