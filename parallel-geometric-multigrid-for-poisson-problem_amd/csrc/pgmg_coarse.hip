@@ -3,8 +3,8 @@
 // A level entered with x0 = 0 (every level below the finest in a V/W-cycle, RECOMP) costs
 // two fused passes: k_pre (x1 = J(0), the check ||r(x1)||, x2 = J(x1), rc = R r(x2)) and
 // k_post (the pre-smoothed iterate recomputed from f, + P ec, two sweeps with the check
-// ||r(x1)||).  pgmg_fused.hip runs them as row-marching bands: right for the bulk levels,
-// where HBM streaming is what counts, but on the small levels (N <= 513: 0.02-0.26 M points)
+// ||r(x1)||).  pgmg_pre.hip / pgmg_post.hip run them as row-marching bands: right for the bulk
+// levels, where HBM streaming is what counts, but on the small levels (N <= 513: 0.02-0.26 M points)
 // the launch spends its ~6 µs in ONE wave's serial chain -- a band of 2 coarse rows marches
 // 12 fine rows (3x redundant) with four stencil stages per row, ~1000 VALU + 700 SALU
 // instructions per wave, one wave per SIMD, nothing to hide the latency behind
@@ -16,13 +16,14 @@
 // The halo is recomputed by neighbouring tiles (~1.7x redundant points at TC = 8), spread
 // over 256 threads instead of serialised in one wave.
 //
-// Semantics are exactly k_pre / k_post's (pgmg_fused.hip pre_body / post_body with
+// Semantics are exactly k_pre / k_post's (pgmg_pre.hip pre_body / pgmg_post.hip post_body with
 // X0_ZERO, RECOMP, no strips, no regenerated f), every value through the reference's
 // expression in its order (MultiGrid.hpp:57-94, Smoother.hpp:59-88, DynamicGridUtils.hpp:
 // 59-69, MultiGrid.hpp:187-226), so the results are bitwise those of the row-marching
 // passes; only the check's per-block partial sums are grouped differently (their order is
 // not part of the contract; the count goes with them into the check's record).
 #include "pgmg.h"
+#include "pgmg_check.h"
 #include "pgmg_coarse.h"
 
 namespace pgmg {
@@ -34,37 +35,8 @@ template <class T> __device__ __forceinline__ double csq(double acc, T r)
     return __builtin_fma((double)r, (double)r, acc);
 }
 
-__device__ __forceinline__ double ctile_block_sum(double v, double *red)
-{
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = 0.0;
-    if (threadIdx.x == 0)
-        for (int i = 0; i < kCT / 64; ++i) s += red[i];
-    return s;
-}
-
-// Early-exit decision of an in-stream check (MODE 2): every workgroup re-reduces the
-// check's partials in the same order (pgmg_fused.hip rare_decide's semantics); workgroup
-// (0,0) books the exit (one sweep less, one exit more) when it fired.
-__device__ __forceinline__ bool ctile_decide(const double *partials, int np, double eps,
-                                             const double *global_sum,
-                                             unsigned long long *stats, double *red, int *trig)
-{
-    double v = 0.0;
-    for (int k = threadIdx.x; k < np; k += kCT) v += partials[k];
-    v = ctile_block_sum(v, red);
-    if (threadIdx.x == 0) *trig = (sqrt(global_sum != nullptr ? *global_sum : v) < eps) ? 1 : 0;
-    __syncthreads();
-    const bool t = *trig != 0;
-    if (t && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && stats != nullptr) {
-        atomicAdd(&stats[0], (unsigned long long)-1LL);
-        atomicAdd(&stats[1], 1ull);
-    }
-    return t;
-}
-
+// (MODE 2's early-exit decision of an in-stream check is check_decide, pgmg_check.h: the one
+// k_pre_rare / k_post_rare take)
 // MODE 0: the pass (two sweeps, the check's partials).  MODE 1: the check predicted to fire
 // (k_pre1 / k_post1): one sweep is the result, the check's partials written, one sweep and one
 // exit booked.  MODE 2: the in-stream rare path (k_pre_rare / k_post_rare): decide the check
@@ -84,7 +56,7 @@ __global__ __launch_bounds__(kCT) void k_pre_tile(CoarseArgsT<T> a)
     __shared__ int trig;
     const bool lead = blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0;
     if constexpr (MODE == 2) {
-        const bool t = ctile_decide(a.dec_partials, a.dec_np, a.eps, a.global_sum, a.stats, red, &trig);
+        const bool t = check_decide<kCT / 64>(a.dec_partials, a.dec_np, a.eps, a.global_sum, a.stats, red, &trig);
         if (lead && a.fired != nullptr) *a.fired = t ? 1u : 0u;
         if (!t) return;
     }
@@ -166,7 +138,7 @@ __global__ __launch_bounds__(kCT) void k_pre_tile(CoarseArgsT<T> a)
         }
     }
     if (MODE != 2) {
-        const double s = ctile_block_sum(acc, red);
+        const double s = block_sum<kCT / 64>(acc, red);
         if (threadIdx.x == 0) a.partials[blockIdx.y * gridDim.x + blockIdx.x] = s;
     }
 }
@@ -189,7 +161,7 @@ __global__ __launch_bounds__(kCT) void k_post_tile(CoarseArgsT<T> a)
     __shared__ int trig;
     const bool lead = blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0;
     if constexpr (MODE == 2) {
-        if (!ctile_decide(a.dec_partials, a.dec_np, a.eps, a.global_sum, a.stats, red, &trig)) return;
+        if (!check_decide<kCT / 64>(a.dec_partials, a.dec_np, a.eps, a.global_sum, a.stats, red, &trig)) return;
     }
     const int N = a.N, Nc = a.Nc;
     const long long P = a.P, Pc = a.Pc;
@@ -279,7 +251,7 @@ __global__ __launch_bounds__(kCT) void k_post_tile(CoarseArgsT<T> a)
         a.x2[y * P + x] = out;
     }
     if (MODE != 2) {
-        const double s = ctile_block_sum(acc, red);
+        const double s = block_sum<kCT / 64>(acc, red);
         if (threadIdx.x == 0) a.partials[blockIdx.y * gridDim.x + blockIdx.x] = s;
     }
 }

@@ -1,4 +1,5 @@
-// pgmg_fused.h — argument blocks of the fused smoother passes (pgmg_fused.hip).
+// pgmg_fused.h — argument blocks and launchers of the fused smoother passes (pgmg_pre.hip,
+// pgmg_post.hip, pgmg_postpre_impl.h, pgmg_fixup.hip; their launch geometry: pgmg_fused.hip).
 // Templates on the grid element type T (double, or float for the fp32 variant);
 // partial sums and eps stay double.
 #pragma once
@@ -71,7 +72,7 @@ struct PostArgsT {
     // calls): also the two-step full weighting of x2 into level 2 (r2out, pitch Pr2, N = Nr2),
     // the next F-cycle's first restriction step.  With the 116-column tile stride and the
     // 6-column margin the pass forms every level-2 centre column itself: lanes 3..60 own the
-    // centres and lane 63 loads its own east coarse column (pgmg_fused.hip "k_post_r2")
+    // centres and lane 63 loads its own east coarse column (pgmg_post.hip "k_post_r2")
     T *r2out;
     long long Pr2;
     int Nr2;
@@ -168,18 +169,5 @@ void launch_smooth4_finish(const PostPreArgsT<T> &a, int np, const double *globa
 void launch_postpre_decide(const double *partials1, const double *partials2,
                            unsigned long long *stats, int np, const double *global, double eps,
                            unsigned *flags, hipStream_t s);
-// out[i] = 1 when check i could fire: sqrt(sum of its partials) < eps * (1 + 1e-12), the
-// sum taken in the fix-ups' order (one workgroup per check); norm[i] = that sqrt
-void launch_verify_checks(const CheckRef *checks, int n, double eps, unsigned *out, double *norm,
-                          hipStream_t s);
-
-// the validation's reply, straight into pinned host memory (no copies): any = OR over the
-// first n_any verdicts, and the n norms and verdicts themselves; then *h_seq = seq (system
-// scope, after the rest: the host polls it)
-void launch_spec_reply(const unsigned *flags, const double *norm, int n, int n_any, unsigned *h_any,
-                       double *h_norm, unsigned *h_flags, unsigned *h_seq, unsigned seq, hipStream_t s);
-// a speculative segment's opening: stats_bk = stats (4 words), flags[0, nflags) = 0
-void launch_spec_open(const unsigned long long *stats, unsigned long long *stats_bk, unsigned *flags,
-                      int nflags, hipStream_t s);
 
 }  // namespace pgmg

@@ -3,7 +3,7 @@
 // that mirror Parallel::ComputeJacobi / ComputeResidual / ComputeRestriction /
 // ComputeProlungator (3_part_parallel/Parallel_Method.cu:144-199) and the per-op study that
 // times them (ParallelTestRunner.cu:231-468); the V-cycle itself uses the aligned, fused
-// passes of pgmg_fused.hip.
+// passes of pgmg_pre.hip / pgmg_post.hip / pgmg_postpre_impl.h.
 //
 // Same streaming scheme as the level kernels (pgmg_kernels.hip), adapted to the caller's
 // layout:
@@ -25,23 +25,10 @@
 // decisions are deterministic run to run.
 #include <algorithm>
 
+#include "pgmg_check.h"
 #include "pgmg_internal.h"
 
 namespace pgmg {
-
-template <int NT>
-__device__ __forceinline__ double gblock_sum(double v, double *red)
-{
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = 0.0;
-    if (threadIdx.x == 0) {
-        #pragma unroll
-        for (int i = 0; i < NT / 64; ++i) s += red[i];
-    }
-    return s;
-}
 
 __device__ __forceinline__ void st_nt1(double *p, double v) { __builtin_nontemporal_store(v, p); }
 // a column pair's 16-byte store (8-byte alignment promised: one global_store_dwordx4 either
@@ -169,7 +156,7 @@ __global__ __launch_bounds__(kBlock) void k_op_sweep(const double *__restrict__ 
     }
     if (SEED && je == H - 1 && act) st2<false>(O + (long long)(H - 1) * Wl + c, w1);
     if (CHECK) {
-        const double s = gblock_sum<kBlock>(acc, red);
+        const double s = block_sum<kWaves>(acc, red);
         if (threadIdx.x == 0) partials[blockIdx.y * gridDim.x + blockIdx.x] = s;
     }
 }
@@ -254,10 +241,8 @@ __global__ __launch_bounds__(kBlock) void k_g_fixup(const double *partials, int 
         if (leader) *done_next = 1u;
         return;
     }
-    double s = 0.0;
-    for (int k = threadIdx.x; k < np; k += kBlock) s += partials[k];
-    s = gblock_sum<kBlock>(s, red);
-    if (threadIdx.x == 0) trig = (sqrt(s) < eps) ? 1 : 0;
+    const double s = partials_sum<kWaves>(partials, np, red);
+    if (threadIdx.x == 0) trig = check_fires(s, eps) ? 1 : 0;
     __syncthreads();
     if (leader) {
         *done_next = trig ? 1u : 0u;
@@ -876,7 +861,7 @@ __global__ __launch_bounds__(kBlock) void k_g_sumsq(const double *v, long long n
     for (long long k = (long long)blockIdx.x * kBlock + threadIdx.x; k < n;
          k += (long long)gridDim.x * kBlock)
         acc += v[k] * v[k];
-    const double s = gblock_sum<kBlock>(acc, red);
+    const double s = block_sum<kWaves>(acc, red);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 

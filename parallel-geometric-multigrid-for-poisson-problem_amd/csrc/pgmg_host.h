@@ -69,6 +69,10 @@ void spec_need_level(pgmg_ctx *c, int l, int gamma, long long *dbl, long long *n
 int spec_reserve(pgmg_ctx *c, long long dbl, long long nchk);
 int spec_validate(pgmg_ctx *c, unsigned *h_out, bool *overflow_out, int n_any);
 int run_cycles_spec(pgmg_ctx *c, int ncycles, int gamma);
+// a speculative segment's opening: stats_bk = stats (4 words), flags[0, nflags) = 0
+// (also opens the F-cycle's segments, pgmg_fcycle.hip)
+void launch_spec_open(const unsigned long long *stats, unsigned long long *stats_bk, unsigned *flags,
+                      int nflags, hipStream_t s);
 
 // --- pgmg_ctx.hip
 void sine_tables(const pgmg_config &cfg, int N, double h, std::vector<double> &sx,

@@ -86,6 +86,7 @@ constexpr int kPostExt = 4;       // row strips: k_post of a level below the fin
                                   // edge (bitwise what the neighbour computes), so the
                                   // coarse correction needs no halo exchange
 constexpr int kBlock = 256;       // threads per block for streaming kernels (4 waves)
+constexpr int kWaves = kBlock / 64;   // (pgmg_check.h block_sum<kWaves>: its unrolled form)
 #ifndef PGMG_TAIL_THREADS
 #define PGMG_TAIL_THREADS 512    // 512 and 1024 measured equal (W at 4097 82.4 vs 82.9 ms)
 #endif

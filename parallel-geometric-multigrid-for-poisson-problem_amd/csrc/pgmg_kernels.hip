@@ -14,25 +14,10 @@
 //     in flight.
 // Expression order follows the reference exactly (file:line at each kernel) and
 // the build uses -ffp-contract=off, so every value is bit-identical to mg_cpu_exec.
+#include "pgmg_check.h"
 #include "pgmg_internal.h"
 
 namespace pgmg {
-
-// deterministic block sum (fixed tree) of one double per thread; result valid in thread 0
-template <int NT>
-__device__ __forceinline__ double block_sum(double v, double *red)
-{
-    v = wave_sum(v);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) red[w] = v;
-    __syncthreads();
-    double s = 0.0;
-    if (threadIdx.x == 0) {
-        #pragma unroll
-        for (int i = 0; i < NT / 64; ++i) s += red[i];
-    }
-    return s;
-}
 
 // ---------------------------------------------------------------------------
 // Jacobi sweep.  Reference: JacobiSmoother::smooth, Smoother.hpp:59-69
@@ -119,7 +104,7 @@ __global__ __launch_bounds__(kBlock) void k_sweep(SweepArgsT<T> a)
         w1 = xn[kU - 1];
     }
     if (NORM) {
-        const double s = block_sum<kBlock>(acc, red);
+        const double s = block_sum<kWaves>(acc, red);
         if (threadIdx.x == 0) a.partials[blockIdx.y * gridDim.x + blockIdx.x] = s;
     }
 }
@@ -346,13 +331,9 @@ __global__ __launch_bounds__(kBlock) void k_fixup(FixupArgsT<T> a)
         if (leader) *a.done_next = 1u;
         return;
     }
-    double s = 0.0;
-    for (int k = threadIdx.x; k < a.np; k += kBlock) s += a.partials[k];
-    s = block_sum<kBlock>(s, red);
-    if (threadIdx.x == 0) {
-        const double tot = a.global_sum != nullptr ? *a.global_sum : s;
-        trig = (sqrt(tot) < a.eps) ? 1 : 0;
-    }
+    const double s = partials_sum<kWaves>(a.partials, a.np, red);
+    if (threadIdx.x == 0)
+        trig = check_fires(a.global_sum != nullptr ? *a.global_sum : s, a.eps) ? 1 : 0;
     __syncthreads();
     if (leader) {
         *a.done_next = trig ? 1u : 0u;
@@ -688,7 +669,7 @@ __global__ __launch_bounds__(kBlock) void k_resnorm(const T *x, const T *f, doub
         const T r = f[q] - ih * (T(4) * x[q] - x[q - 1] - x[q + 1] - x[q - P] - x[q + P]);
         acc += sq(r);
     }
-    const double s = block_sum<kBlock>(acc, red);
+    const double s = block_sum<kWaves>(acc, red);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 
@@ -703,9 +684,7 @@ __global__ __launch_bounds__(kBlock) void k_sum_partials(const double *partials,
                                                          double *out)
 {
     __shared__ double red[kBlock / 64];
-    double s = 0.0;
-    for (int k = threadIdx.x; k < np; k += kBlock) s += partials[k];
-    s = block_sum<kBlock>(s, red);
+    const double s = partials_sum<kWaves>(partials, np, red);
     if (threadIdx.x == 0) *out = s;
 }
 

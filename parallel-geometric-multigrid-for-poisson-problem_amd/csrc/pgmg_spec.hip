@@ -1,6 +1,7 @@
 // pgmg_spec.hip — "speculative calls": a call's early-exit checks recorded instead of decided
 // in-stream and validated once after it (pinned reply, reply_wait), the per-level policy with
-// "predicted to fire", segment planning, run_cycles_spec, the read-only queries.  Host only.
+// "predicted to fire", segment planning, run_cycles_spec, the read-only queries.  Host code and
+// the validation's three small kernels (k_verify_checks, k_spec_reply, k_spec_open).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -9,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "pgmg_check.h"
 #include "pgmg_host.h"
 
 using namespace pgmg;
@@ -33,6 +35,93 @@ using namespace pgmg;
 // the solver is near convergence, where checks keep firing).  Results and statistics
 // are therefore always the exact path's.  The call ends with one host synchronisation.
 // ---------------------------------------------------------------------------
+
+namespace pgmg {
+
+// Validation of a speculative call: one workgroup per recorded check re-reduces its
+// partials with the sum every in-stream decision takes (partials_sum, pgmg_check.h: 256
+// threads, strided, then the block sum) and flags the checks that could fire.  The 1e-12
+// margin makes the flag a superset of "fires" whatever order the exact path sums in (an
+// all-rank sum of row strips goes through launch_sum_partials + allreduce: relative
+// differences below ~4e-13 for the <= 3072 non-negative terms of one rank).
+// out[i] = 1 when check i's prediction may be wrong; norm[i] = sqrt(sum of its partials)
+__global__ __launch_bounds__(256) void k_verify_checks(const CheckRef *checks, double eps,
+                                                       unsigned *out, double *norm)
+{
+    __shared__ double red[4];
+    const CheckRef c = checks[blockIdx.x];
+    const double s = partials_sum(c.partials, c.np, red);
+    if (threadIdx.x == 0) {
+        // flag = the prediction may be wrong: "does not fire" checks that could fire, "fires"
+        // checks that could not (same margin the other way); in-stream checks are logged
+        // for the norms only
+        const bool could_fire = sqrt(s) < eps * (1.0 + 1e-12);
+        const bool must_fire = sqrt(s) < eps * (1.0 - 1e-12);
+        out[blockIdx.x] = c.expect == 0 ? (could_fire ? 1u : 0u)
+                                        : (c.expect == 1 ? (must_fire ? 0u : 1u) : 0u);
+        norm[blockIdx.x] = sqrt(s);
+    }
+}
+
+static void launch_verify_checks(const CheckRef *checks, int n, double eps, unsigned *out,
+                                 double *norm, hipStream_t s)
+{
+    if (n > 0) k_verify_checks<<<dim3(n), dim3(256), 0, s>>>(checks, eps, out, norm);
+}
+
+// The validation's reply (after the all-rank MIN): any = 1 when one of the first n_any checks
+// could fire on every rank, then every check's norm and verdict, each stored straight into
+// the context's pinned host staging -- the call then waits for the stream once, with no copy
+// operations between the kernels and the wait.
+__global__ __launch_bounds__(256) void k_spec_reply(const unsigned *f, const double *norm, int n,
+                                                    int n_any, unsigned *h_any, double *h_norm,
+                                                    unsigned *h_flags, unsigned *h_seq, unsigned seq)
+{
+    __shared__ unsigned any;
+    if (threadIdx.x == 0) any = 0u;
+    __syncthreads();
+    unsigned v = 0u;
+    for (int k = threadIdx.x; k < n; k += blockDim.x) {
+        const unsigned fk = f[k];
+        if (k < n_any) v |= fk;
+        h_flags[k] = fk;
+        h_norm[k] = norm[k];
+    }
+    if (v) atomicOr(&any, 1u);
+    __syncthreads();
+    if (threadIdx.x == 0) *h_any = any;
+    // every store above reaches the host before the sequence word (the host polls it)
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0) __hip_atomic_store(h_seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// any = OR over the first n_any verdicts, and the n norms and verdicts themselves, straight
+// into pinned host memory; then *h_seq = seq (system scope, after the rest)
+static void launch_spec_reply(const unsigned *flags, const double *norm, int n, int n_any,
+                              unsigned *h_any, double *h_norm, unsigned *h_flags, unsigned *h_seq,
+                              unsigned seq, hipStream_t s)
+{
+    k_spec_reply<<<dim3(1), dim3(256), 0, s>>>(flags, norm, n, n_any, h_any, h_norm, h_flags, h_seq,
+                                                seq);
+}
+
+// a speculative segment's opening: stats_bk = stats (4 words), flags[0, nflags) = 0
+__global__ __launch_bounds__(256) void k_spec_open(const unsigned long long *stats,
+                                                   unsigned long long *stats_bk, unsigned *flags,
+                                                   int nflags)
+{
+    if (threadIdx.x < 4) stats_bk[threadIdx.x] = stats[threadIdx.x];
+    for (int k = threadIdx.x; k < nflags; k += blockDim.x) flags[k] = 0u;
+}
+
+void launch_spec_open(const unsigned long long *stats, unsigned long long *stats_bk, unsigned *flags,
+                      int nflags, hipStream_t s)
+{
+    k_spec_open<<<dim3(1), dim3(256), 0, s>>>(stats, stats_bk, flags, nflags);
+}
+
+}  // namespace pgmg
 
 void pgmg::spec_need_level(pgmg_ctx *c, int l, int gamma, long long *dbl, long long *nchk)
 {

@@ -1,6 +1,7 @@
 #!/bin/bash
 # Build a measurement variant of the library: libpgmg_<name>.so = the sources with
-# -DPGMG_TUNING and extra -D flags (compile-time A/B of pgmg_fused.hip variants).
+# -DPGMG_TUNING and extra -D flags (compile-time A/B of the fused passes' variants:
+# the PGMG_* switches of csrc/pgmg_fused_dev.h and pgmg_postpre_impl.h).
 #   scripts/build_variant.sh NAME "-DPGMG_PP_BUF=0 ..."
 set -e
 NAME=$1; shift

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Sweep launch variants of the fused smoother passes in ONE process (interleaved rounds).
 
-For every variant (environment knobs read by pgmg_fused.hip at launch time) it checks
+For every variant (environment knobs the fused passes' launchers read at launch time:
+tuning_int in csrc/pgmg_fused.hip, pgmg_pre.hip, pgmg_post.hip, pgmg_postpre_impl.h) it checks
 bit-parity at N=4097 against the reference golden hash, then times the finest-level
 k_pre / k_post kernels and the whole V-cycle at N=16385 with hipEvents.
 

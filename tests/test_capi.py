@@ -156,3 +156,14 @@ def test_library_built_from_this_tree(pgmg):
     import _pkgload
     assert pgmg.load().pgmg_source_hash().decode() == _pkgload.source_hash()
 
+
+def test_makefile_srcs_are_the_hip_files():
+    """The Makefile's SRCS line (what is compiled, and what the source hash covers) lists
+    exactly the csrc/*.hip files: a file split off but not listed would not be built, a leftover
+    never built would sit outside the hash."""
+    import _pkgload
+    mk = (_pkgload.PKG_DIR / "Makefile").read_text()
+    srcs = re.search(r"^SRCS = (.*)$", mk, re.M).group(1).split()
+    assert len(srcs) == len(set(srcs)), "a file is listed twice"
+    assert set(srcs) == {p.name for p in (_pkgload.PKG_DIR / "csrc").glob("*.hip")}
+
