@@ -456,6 +456,31 @@ int pgmg_damp_time(pgmg_ctx *ctx, double omega, int reps, double *ms_per_pass, d
  * time.  The restricted f chain and the grids of the levels below the tail's top are allocated
  * on the first call (about 1/3 of a level-0 grid). */
 int pgmg_fmg(pgmg_ctx *ctx, int nu);
+/* ---- Damped full multigrid --------------------------------------------------------------
+ * pgmg_fmg's cycles use the undamped smoother, which leaves the checkerboard error of every
+ * level untouched: on an f that holds it (any but the smooth analytic one) plain FMG stops at
+ * ||r|| / ||f|| ~ 1e-1.  pgmg_fmg_damped(ctx, nu, omega) is pgmg_fmg with step 3 changed to
+ *   3. for l = L-1 .. 0: u_l = C(u_{l+1}), then nu x { v_cycle(u_l, f_l, N_l, h_l);
+ *                                                     u_l <- damp(u_l, f_l, h_l, omega) }
+ * damp is pgmg_damp's formula on that level: u + w * r with r = f_l - ih_l (4u - ...),
+ * w = (T)(omega * 0.25 * (h_l * h_l)), out-of-place semantics, the boundary never written, two
+ * roundings, no fused multiply-add, in the context's element type.  The coarsest level (step 2)
+ * is not damped.  With omega = 1/2 and nu = 2 the result has ||r|| / ||f|| ~ 1e-3 on a random f
+ * (tests/test_fmg_damped_cpu.py: 80-150 times below plain FMG) and, on the analytic problem,
+ * the same 0.9 x discretisation error as plain FMG, for 2 nu / (1 - 1/4) damping passes' worth
+ * of extra finest-level traffic; a damped solve that starts from it needs 4-6 cycles to
+ * rtol 1e-6 where one from zero needs 11-13.
+ * Everything else is pgmg_fmg's contract: nu < 1, n_coarse < 5 (N_L = 3) or a null context:
+ * PGMG_ERR_ARG; omega not finite, <= 0 or > 1: PGMG_ERR_ARG; before pgmg_set_problem*:
+ * PGMG_ERR_STATE; world > 1: PGMG_ERR_STATE; all before anything is enqueued.  fp64 and fp32;
+ * problems set with pgmg_set_problem and pgmg_set_problem_device (the climb and every damp run
+ * on the context's grids, never on the caller's array; the result is copied out, synchronous).
+ * Otherwise asynchronous on the context's stream: the damps compute no norm, copy nothing and
+ * wait for nothing.  Every early-exit check is decided in-stream; the sweep and early-exit
+ * statistics are those of the cycles alone.  It drops the carry and resets the speculation
+ * history.  f is left untouched.  The damping pass's side buffer is allocated on the first
+ * call. */
+int pgmg_fmg_damped(pgmg_ctx *ctx, int nu, double omega);
 /* Measurement: `reps` cubic interpolation passes level 1 -> level 0 back to back on the
  * context's stream between two hipEvents, after two warm ones; mean device ms per pass and its
  * algorithmic bytes (one element per fine point written + one per coarse point read).  Needs
@@ -586,6 +611,19 @@ int pgmg_prolong_grid(const double *d_coarse, double *d_fine, int Nc, int Nf, in
                       int num_thread, void *stream);
 int pgmg_norm(const double *d_v, long long n, double *result, void *stream);
 int pgmg_rhs(double *d_f, int W, int H, double h, double a, double p, double q, void *stream);
+/* One damping pass (pgmg_damp's formula, above) on caller-owned N x N device arrays, pitch N,
+ * fp64:  x <- x + w * r,  r = f - ih (4x - x_l - x_r - x_u - x_d),  ih = 1.0 / (h * h),
+ * w = omega * 0.25 * (h * h), on every interior point; out-of-place semantics (every r from the x
+ * of before the pass), two roundings, the boundary never written.  It is the launch the damped
+ * FMG runs on every level of its pyramid, so N = 2^k + 1 with k >= 2, and h is the level's
+ * (h_0 * 2^l on level l).  res_norm != NULL: the residual norm of x BEFORE the update, bit for
+ * bit what pgmg_monitor(PGMG_MON_RESIDUAL) returns for that state on a context of that N and h
+ * (the decomposition is a function of N alone); the call is then synchronous.  res_norm == NULL:
+ * asynchronous on `stream`.  Another N, omega not finite or outside (0, 1], h not finite or
+ * <= 0, a null x or f: PGMG_ERR_ARG, nothing enqueued.  Its scratch (the deferred edges, the
+ * partial sums) belongs to the per-stream set below. */
+int pgmg_damp_grid(double *d_x, const double *d_f, int N, double h, double omega, double *res_norm,
+                   void *stream);
 /* The op-level entries keep one scratch set (partial sums, flags, ping-pong buffer) per
  * stream they were called on; this waits for `stream` and frees its set (a later op on the
  * same stream allocates a fresh one).  Call it before destroying a stream the ops used. */

@@ -230,7 +230,7 @@ class Solver:
     def fcycle(self, n=1):
         check(self.lib.pgmg_fcycle(self.h, int(n)), "pgmg_fcycle")
 
-    def fmg(self, nu=2):
+    def fmg(self, nu=2, damp=None):
         """Replace phi with the full-multigrid solution of the problem's own right-hand side
         (pgmg_fmg): f restricted down the pyramid, the coarsest level solved from zero, then per
         level the cubic interpolation of the coarser solution and `nu` V-cycles.  The current
@@ -239,8 +239,14 @@ class Solver:
 
             s.set_problem(None, f); s.fmg(); s.solve(rtol=1e-8)
 
-        One GPU only."""
-        check(self.lib.pgmg_fmg(self.h, int(nu)), "pgmg_fmg")
+        damp: None is pgmg_fmg exactly; an omega in (0, 1] (0.5 recommended) follows every
+        V-cycle of the climb with a damping pass on that level (pgmg_fmg_damped), which removes
+        the checkerboard error the undamped smoother leaves: for any right-hand side but the
+        smooth analytic one the residual is about 100 times smaller.  One GPU only."""
+        if damp is None:
+            check(self.lib.pgmg_fmg(self.h, int(nu)), "pgmg_fmg")
+        else:
+            check(self.lib.pgmg_fmg_damped(self.h, int(nu), float(damp)), "pgmg_fmg_damped")
 
     def fmg_interp_time(self, reps=20):
         """(mean device ms, algorithmic bytes) of the cubic interpolation pass level 1 ->
@@ -318,13 +324,22 @@ class Solver:
         return ms.value, b.value
 
     def solve(self, cycle="V", rtol=1e-3, atol=0.0, max_cycles=30, check_every=1,
-              stall_ratio=0.0, stall_checks=2, error=False, damp=0.0):
+              stall_ratio=0.0, stall_checks=2, error=False, damp=0.0, start=None, nu=2):
         """Cycle until the residual norm is at most max(atol, rtol * r0), the cycle cap, a
         stall or a non-finite norm (pgmg_solve; the stop rule: include/pgmg.h).  Returns the
         PgmgSolveInfo with a `.history` list of (cycle, res, rel_error), check 0 first.
         damp: 0.0 is pgmg_solve exactly; a positive omega (0.5 recommended) makes every check a
         damping pass (pgmg_solve_damped), which converges for any right-hand side; phi afterwards
-        is the damped last iterate, its residual norm at most info.res."""
+        is the damped last iterate, its residual norm at most info.res.
+        start: None starts from the current phi; "fmg" first replaces it with fmg(nu, damp)
+        (damped when damp is positive), so check 0 -- and r0 of the rule -- is the FMG iterate's
+        and info.cycles counts the cycles after it.  rtol is then relative to a residual FMG has
+        already brought down (by ~1e-3 with damp=0.5): give the target as atol to compare with
+        a solve from zero."""
+        if start not in (None, "fmg"):
+            raise ValueError(f"start must be None or 'fmg', not {start!r}")
+        if start == "fmg":
+            self.fmg(nu, damp if damp != 0.0 else None)
         o = PgmgSolveOpts()
         check(self.lib.pgmg_solve_opts_default(C.byref(o)), "pgmg_solve_opts_default")
         kinds = {"V": PGMG_CYCLE_V, "W": PGMG_CYCLE_W, "F": PGMG_CYCLE_F}
@@ -572,6 +587,17 @@ class _Ops:
         out = C.c_double()
         check(load().pgmg_norm(self._ptr(v), v.numel(), C.byref(out), stream), "pgmg_norm")
         return out.value
+
+    def damp(self, x, f, h, omega=0.5, stream=None, norm=True):
+        """One damping pass x <- x + omega (h^2/4) r on N x N float64 device arrays
+        (pgmg_damp_grid; N = 2^k + 1, k >= 2).  norm=True: returns the residual norm of x before
+        the update (synchronous); norm=False: returns None, asynchronous on `stream`."""
+        N = x.shape[0]
+        assert tuple(x.shape) == (N, N) and tuple(f.shape) == (N, N), (x.shape, f.shape)
+        out = C.c_double()
+        check(load().pgmg_damp_grid(self._ptr(x), self._ptr(f), N, float(h), float(omega),
+                                    C.byref(out) if norm else None, stream), "pgmg_damp_grid")
+        return out.value if norm else None
 
     def rhs(self, f, h, a=1.0, p=1.0, q=1.0, stream=None):
         H, W = f.shape

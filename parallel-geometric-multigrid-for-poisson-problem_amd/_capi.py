@@ -146,6 +146,7 @@ SIGNATURES = [
                                     C.POINTER(PgmgSolveInfo)]),
     ("pgmg_damp_time", C.c_int, [_P, C.c_double, C.c_int, _DP, _DP]),
     ("pgmg_fmg", C.c_int, [_P, C.c_int]),
+    ("pgmg_fmg_damped", C.c_int, [_P, C.c_int, C.c_double]),
     ("pgmg_fmg_interp_time", C.c_int, [_P, C.c_int, _DP, _DP]),
     ("pgmg_stats", C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     ("pgmg_stats_detail", C.c_int, [_P, C.POINTER(C.c_longlong)]),
@@ -180,6 +181,7 @@ SIGNATURES = [
     ("pgmg_norm", C.c_int, [_P, C.c_longlong, _DP, _P]),
     ("pgmg_rhs", C.c_int, [_P, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
                            _P]),
+    ("pgmg_damp_grid", C.c_int, [_P, _P, C.c_int, C.c_double, C.c_double, _DP, _P]),
     ("pgmg_ops_release", C.c_int, [_P]),
     ("pgmg_device_alloc", C.c_int, [C.POINTER(_P), C.c_size_t]),
     ("pgmg_device_free", C.c_int, [_P]),

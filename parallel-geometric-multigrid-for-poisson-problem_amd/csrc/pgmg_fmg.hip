@@ -9,7 +9,10 @@
 // but the interpolation is the existing machinery: launch_restrict_values for the f chain, the
 // LDS tail (one launch per level at or below the tail's top, that level as its top) and
 // enqueue_cycle from a bulk level with the level's restricted f standing in for lv[l].F.
+// pgmg_fmg_damped is the same climb with the damping pass (pgmg_monitor.hip, fmg_damp_level)
+// after every V-cycle of it, on that level's grids.
 #include <algorithm>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -252,9 +255,11 @@ struct FmgLevelF {
     }
 };
 
+// omega > 0 (pgmg_fmg_damped): one damping pass after every V-cycle of the climb
 template <class T>
-static int fmg_enqueue(pgmg_ctx *c, int nu)
+static int fmg_enqueue(pgmg_ctx *c, int nu, double omega)
 {
+    const bool damped = omega > 0.0;
     const int nb = c->nb, Lc = (int)c->fmg_lv.size() - 1;
     const std::vector<Level> &lv = c->fmg_lv;
     // 1. the f chain, level by level (every level's values are used)
@@ -263,26 +268,35 @@ static int fmg_enqueue(pgmg_ctx *c, int nu)
                                lv[l + 1].P, c->s);
     // nu V-cycles of a level at or below the tail's top: one k_tail launch with that level as
     // its top (at N <= n_coarse the coarsest smoother call)
-    auto tail_level = [&](int l, bool from_global) -> int {
+    auto tail_level = [&](int l, bool from_global, int visits) -> int {
         TailArgsT<T> t = tail_args<T>(c);
         t.f_top = G<T>(fmg_f(c, l));
         t.e_top = G<T>(fmg_u(c, l));
         t.P_top = lv[l].P;
         t.N_top = lv[l].N;
         t.h_top = lv[l].h;
-        t.visits = nu;
+        t.visits = visits;
         t.x0_from_global = from_global ? 1 : 0;
         HIPC(launch_tail_gamma(t, 1, c->s));
         return PGMG_OK;
     };
     // 2. the coarsest level from zero (the tail starts from zero in LDS and stores every point)
-    PGMG_TRY(tail_level(Lc, false));
+    PGMG_TRY(tail_level(Lc, false, nu));
     // 3. the climb
     for (int l = Lc - 1; l >= 0; --l) {
         PGMG_TRY(launch_interp_cubic(G<T>(fmg_u(c, l + 1)), lv[l + 1].N, lv[l + 1].P,
                                      G<T>(fmg_u(c, l)), lv[l].P, c->s));
+        const bool gen = l == 0 && c->rgfx != nullptr;   // level 0's analytic f: regenerated
         if (l >= nb) {
-            PGMG_TRY(tail_level(l, true));
+            if (!damped) {
+                PGMG_TRY(tail_level(l, true, nu));
+                continue;
+            }
+            // a damp between the cycles: one launch per cycle, each from the damped grid
+            for (int k = 0; k < nu; ++k) {
+                PGMG_TRY(tail_level(l, true, 1));
+                PGMG_TRY(fmg_damp_level(c, fmg_u(c, l), fmg_f(c, l), lv[l], omega, gen));
+            }
             continue;
         }
         // u_l has a zero boundary (u_L = 0 and C keeps it): the level's other grids mirror it
@@ -290,32 +304,51 @@ static int fmg_enqueue(pgmg_ctx *c, int nu)
         launch_zero_frame(G<T>(L.B), L.P, L.N, c->s);
         if (l == 0 && c->S.base) launch_zero_frame(G<T>(c->S), L.P, L.N, c->s);
         const FmgLevelF stand_in(c, l);
+        // the damp of what a cycle left: every cycle ends with its iterate under lv[l].A, but
+        // which grid that is may change (the cross-fused cycles swap the roles of A / B / S), so
+        // the grids are read here, after the cycle; f is the stand-in
+        auto damp = [&]() -> int {
+            return fmg_damp_level(c, c->lv[l].A, c->lv[l].F, lv[l], omega, gen);
+        };
         // a cross-fused context runs level 0's nu cycles as k_pre, (k_postpre) x (nu - 1), k_post
         // (one finest pass per further cycle instead of two), every check in-stream
         if (l == 0 && c->cross) {
-            PGMG_TRY(run_cycles_plain(c, nu, 1, false));
+            if (!damped) {
+                PGMG_TRY(run_cycles_plain(c, nu, 1, false));
+                continue;
+            }
+            // (a damp between the cycles: nu calls of one cycle, k_pre .. k_post each)
+            for (int k = 0; k < nu; ++k) {
+                PGMG_TRY(run_cycles_plain(c, 1, 1, false));
+                PGMG_TRY(damp());
+            }
             continue;
         }
-        for (int k = 0; k < nu; ++k) PGMG_TRY(enqueue_cycle(c, l, 1, false));
+        for (int k = 0; k < nu; ++k) {
+            PGMG_TRY(enqueue_cycle(c, l, 1, false));
+            if (damped) PGMG_TRY(damp());
+        }
     }
     return PGMG_OK;
 }
 
-}  // namespace pgmg
-
-extern "C" {
-
-int pgmg_fmg(pgmg_ctx *c, int nu)
+// pgmg_fmg (omega = 0) and pgmg_fmg_damped
+static int fmg_run(pgmg_ctx *c, int nu, double omega, const char *who_)
 {
+    const std::string who(who_);
     if (!c) return set_err(PGMG_ERR_ARG, "null ctx");
-    if (nu < 1) return set_err(PGMG_ERR_ARG, "pgmg_fmg: nu must be at least 1");
+    if (nu < 1) return set_err(PGMG_ERR_ARG, who + ": nu must be at least 1");
+    if (omega != 0.0) PGMG_TRY(damp_omega_check(omega, who_));
     if (fmg_coarsest_n(c) < 5)
-        return set_err(PGMG_ERR_ARG, "pgmg_fmg: the coarsest level needs 5 points per side for the "
-                                     "cubic interpolation (n_coarse >= 5)");
+        return set_err(PGMG_ERR_ARG, who + ": the coarsest level needs 5 points per side for the "
+                                           "cubic interpolation (n_coarse >= 5)");
     if (!c->have_problem) return set_err(PGMG_ERR_STATE, "pgmg_set_problem first");
     if (c->cfg.world > 1)
-        return set_err(PGMG_ERR_STATE, "pgmg_fmg: one GPU only (world 1); row strips are not supported");
+        return set_err(PGMG_ERR_STATE, who + ": one GPU only (world 1); row strips are not supported");
     PGMG_TRY(fmg_setup(c));
+    // the damping pass's side buffer and partials, sized for level 0 (the largest) before
+    // anything is enqueued
+    if (omega != 0.0) PGMG_TRY(fmg_damp_reserve(c, c->cfg.N));
     // an entry that changes phi: the carry goes, the speculation starts over (the statistics
     // continue)
     c->carry = false;
@@ -326,7 +359,7 @@ int pgmg_fmg(pgmg_ctx *c, int nu)
     const bool ext = c->ext_phi != nullptr;
     if (ext) PGMG_TRY(ext_stage_in(c, false));
     HIPC(hipEventRecord(c->ev0, c->s));
-    PGMG_TRY(c->fp32 ? fmg_enqueue<float>(c, nu) : fmg_enqueue<double>(c, nu));
+    PGMG_TRY(c->fp32 ? fmg_enqueue<float>(c, nu, omega) : fmg_enqueue<double>(c, nu, omega));
     HIPC(hipGetLastError());
     HIPC(hipEventRecord(c->ev1, c->s));
     if (ext) {
@@ -334,6 +367,19 @@ int pgmg_fmg(pgmg_ctx *c, int nu)
         PGMG_TRY(stream_wait(c));
     }
     return PGMG_OK;
+}
+
+}  // namespace pgmg
+
+extern "C" {
+
+int pgmg_fmg(pgmg_ctx *c, int nu) { return fmg_run(c, nu, 0.0, "pgmg_fmg"); }
+
+int pgmg_fmg_damped(pgmg_ctx *c, int nu, double omega)
+{
+    // (omega = 0 is no damped call: refused here, fmg_run reads it as pgmg_fmg)
+    if (omega == 0.0) return damp_omega_check(omega, "pgmg_fmg_damped");
+    return fmg_run(c, nu, omega, "pgmg_fmg_damped");
 }
 
 int pgmg_fmg_interp_time(pgmg_ctx *c, int reps, double *ms_per_pass, double *bytes)

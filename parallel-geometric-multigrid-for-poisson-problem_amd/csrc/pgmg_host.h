@@ -82,6 +82,12 @@ int order_after_caller(pgmg_ctx *c);
 int ext_stage_in(pgmg_ctx *c, bool inplace);
 int ext_stage_out(pgmg_ctx *c);
 
+// --- pgmg_monitor.hip
+// the damping pass on a level of the FMG pyramid (no norm, nothing waits); fmg_damp_reserve
+// sizes the context's side buffer and partials for a level of N points beforehand
+int fmg_damp_reserve(pgmg_ctx *c, int N);
+int fmg_damp_level(pgmg_ctx *c, const Grid &u, const Grid &f, const Level &L, double omega, bool gen);
+
 // the tail launch's arguments every caller shares (visits, x0_from_global, fmg_*: the caller's)
 template <class T>
 inline TailArgsT<T> tail_args(const pgmg_ctx *c)

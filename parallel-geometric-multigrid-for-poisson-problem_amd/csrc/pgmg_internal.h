@@ -284,4 +284,19 @@ void launch_g_sumsq(const double *v, long long n, double *partials, int nblocks,
 void launch_g_rhs(double *f, const double *sx, const double *sy, double factor, int W, int H,
                   hipStream_t s);
 
+// The damping pass on ANY grid pair of N points per side (pgmg_monitor.hip "The damping pass on
+// any level"): an FMG level of a context, or the caller's arrays of pgmg_damp_grid.  x and f:
+// element (0, 0), pitches Px / Pf elements; ih and h the level's; gfx / gsy non-null: f is
+// regenerated as (T)(gfx[i] * gsy[j]) instead of read.  partials: 3 * damp_grid_blocks(N)
+// doubles; side: damp_grid_side_elems(N) elements of T; sums non-null: the three totals land
+// there (one more launch), [0] = sum r^2 of x before the update.
+// omega of every damping entry: finite, in (0, 1] (PGMG_ERR_ARG otherwise)
+int damp_omega_check(double omega, const char *who);
+int damp_grid_blocks(int N);
+size_t damp_grid_side_elems(int N);
+template <class T>
+void launch_damp_grid(T *x, long long Px, const T *f, long long Pf, int N, double ih, double h,
+                      double omega, const double *gfx, const double *gsy, double *partials, T *side,
+                      double *sums, hipStream_t s);
+
 }  // namespace pgmg

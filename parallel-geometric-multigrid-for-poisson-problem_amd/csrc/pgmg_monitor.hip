@@ -335,18 +335,79 @@ static void mon_launch_mode(const MonArgsT<T, SX, SF> &a, unsigned mode, dim3 g,
     }
 }
 
-// Enqueue the pass and the reduction of its partials: the three totals land in c->mon_buf +
-// 3 * c->mon_cap.  phi and f are read where they lie: the level-0 grids, or the caller's arrays
-// of a device-bound problem (pitch N, double).  omega > 0: the damping pass (what includes the
-// residual), which writes phi there too, and the scatter of its deferred outputs.
-template <class T>
-static int mon_enqueue(pgmg_ctx *c, unsigned what, double omega = 0.0)
+// the deferred outputs of a damping pass into x: ~4 columns per thread of a row, ~16 rows per
+// thread of a tile boundary
+template <class T, class SX>
+static void mon_scatter(SX *x, long long Px, const T *sr, const T *sc, int N, int lo, int hi, int u0,
+                        int u1, const MonGrid &mg, hipStream_t s)
 {
-    const Level &L = c->lv[0];
-    const MonGrid mg = mon_grid(L.N, L.lo, L.hi);
-    const int np = mg.tiles * mg.bands;
-    const bool damp = omega > 0.0;
-    const size_t side = damp ? mon_side_elems(L.N, mg) * sizeof(T) : 0;
+    const int bxr = std::max(1, (N + 4 * kBlock - 1) / (4 * kBlock));
+    const int bxc = std::max(1, (N + 16 * kBlock - 1) / (16 * kBlock));
+    k_mon_scatter_rows<T, SX><<<dim3(bxr, 2 * mg.bands), dim3(kBlock), 0, s>>>(x, Px, sr, N, lo, hi,
+                                                                               u0, u1, mg.bands);
+    if (mg.tiles > 1)
+        k_mon_scatter_cols<T, SX><<<dim3(bxc, mg.tiles - 1), dim3(kBlock), 0, s>>>(x, Px, sc, N, u0,
+                                                                                   u1);
+}
+
+// The damping pass on any level: a whole grid of N = 2^k + 1 points per side, k >= 2 (rows
+// [0, N), the interior updated), in T, wherever it lies.  The decomposition is mon_grid's, a
+// function of N alone, so the partial sums -- and the norm -- are those of the monitor of a
+// context of that N.  At the small end (N = 5, 9: npairs = 2, 4) one workgroup runs: wave 0
+// holds every column, waves 1 .. 3 have nw = 0 -- their row loads are buffer loads of zero
+// records (nothing is read, whatever the address), their edge-column loads are off (`on`,
+// has_right) and they store nothing, but they march the band and meet every barrier.  N = 65 is
+// two bands: the second holds row 64 alone, which is a boundary row (r >= u1): it is neither
+// updated nor deferred, and k_mon_scatter_rows skips its slots; band 0 defers row 63 (a band
+// lies below it) and the scatter writes it.
+int damp_grid_blocks(int N)
+{
+    const MonGrid mg = mon_grid(N, 0, N);
+    return mg.tiles * mg.bands;
+}
+size_t damp_grid_side_elems(int N) { return mon_side_elems(N, mon_grid(N, 0, N)); }
+
+template <class T>
+void launch_damp_grid(T *x, long long Px, const T *f, long long Pf, int N, double ih, double h,
+                      double omega, const double *gfx, const double *gsy, double *partials, T *side,
+                      double *sums, hipStream_t s)
+{
+    const MonGrid mg = mon_grid(N, 0, N);
+    MonArgsT<T, T, T> a{};
+    a.x = a.xw = x;
+    a.Px = Px;
+    a.f = f;
+    a.Pf = Pf;
+    a.gfx = gfx;
+    a.gsy = gsy;
+    a.partials = partials;
+    a.ih = (T)ih;
+    a.N = N;
+    a.lo = 0;
+    a.hi = N;
+    a.u0 = 1;
+    a.u1 = N - 1;
+    a.sr = side;
+    a.sc = side + (size_t)2 * mg.bands * N;
+    // omega * 0.25 * (h * h) in double, left to right, then the element type
+    a.w = (T)(omega * 0.25 * (h * h));
+    const dim3 g(mg.tiles, mg.bands);
+    if (gfx != nullptr) k_monitor<T, T, T, kMonDamp | kMonRes | kMonGen><<<g, dim3(kBlock), 0, s>>>(a);
+    else k_monitor<T, T, T, kMonDamp | kMonRes><<<g, dim3(kBlock), 0, s>>>(a);
+    mon_scatter<T, T>(x, Px, a.sr, a.sc, N, 0, N, 1, N - 1, mg, s);
+    if (sums != nullptr)
+        k_mon_reduce<<<dim3(1), dim3(kBlock), 0, s>>>(partials, mg.tiles * mg.bands, sums);
+}
+template void launch_damp_grid<double>(double *, long long, const double *, long long, int, double,
+                                       double, double, const double *, const double *, double *,
+                                       double *, double *, hipStream_t);
+template void launch_damp_grid<float>(float *, long long, const float *, long long, int, double,
+                                      double, double, const double *, const double *, double *,
+                                      float *, double *, hipStream_t);
+
+// the context's partials (np workgroups) and, for a damping pass, its side buffer (side bytes)
+static int mon_reserve(pgmg_ctx *c, int np, size_t side)
+{
     if (side > c->mon_side_bytes) {
         if (c->mon_side) HIPC(hipFree(c->mon_side));
         c->mon_side = nullptr;
@@ -363,6 +424,55 @@ static int mon_enqueue(pgmg_ctx *c, unsigned what, double omega = 0.0)
             return set_err(PGMG_ERR_NOMEM, "monitor partials");
         c->mon_cap = np;
     }
+    return PGMG_OK;
+}
+
+// One damping pass on a level of the FMG pyramid (pgmg_fmg_damped): u and f the level's grids
+// as they lie now, L its geometry; gen: level 0's analytic f regenerated.  No norm: the
+// reduction is skipped, nothing is copied and nothing waits.  The side buffer and the partials
+// grow to the largest level asked for (the climb asks for level 0 first, fmg_damp_reserve).
+int fmg_damp_reserve(pgmg_ctx *c, int N)
+{
+    return mon_reserve(c, damp_grid_blocks(N), damp_grid_side_elems(N) * (c->fp32 ? 4 : 8));
+}
+template <class T>
+static int fmg_damp_level_t(pgmg_ctx *c, const Grid &u, const Grid &f, const Level &L, double omega,
+                            bool gen)
+{
+    PGMG_TRY(mon_reserve(c, damp_grid_blocks(L.N), damp_grid_side_elems(L.N) * sizeof(T)));
+    // every row and column the pass reads or writes lies inside the level's grids
+    PGMG_TRY(check_span(G<T>(u), L.P, (int)sizeof(T), 0, L.N - 1, 0, L.N - 1, "damping pass u"));
+    if (!gen) PGMG_TRY(check_span(G<T>(f), L.P, (int)sizeof(T), 0, L.N - 1, 0, L.N - 1, "damping pass f"));
+    launch_damp_grid<T>(G<T>(u), L.P, G<T>(f), L.P, L.N, L.ih, L.h, omega, gen ? c->rgfx : nullptr,
+                        gen ? c->rgsy : nullptr, c->mon_buf, static_cast<T *>(c->mon_side), nullptr,
+                        c->s);
+    return PGMG_OK;
+}
+int fmg_damp_level(pgmg_ctx *c, const Grid &u, const Grid &f, const Level &L, double omega,
+                   bool gen)
+{
+    return c->fp32 ? fmg_damp_level_t<float>(c, u, f, L, omega, gen)
+                   : fmg_damp_level_t<double>(c, u, f, L, omega, gen);
+}
+int damp_omega_check(double omega, const char *who)
+{
+    if (!std::isfinite(omega) || omega <= 0.0 || omega > 1.0)
+        return set_err(PGMG_ERR_ARG, std::string(who) + ": omega must be in (0, 1]");
+    return PGMG_OK;
+}
+
+// Enqueue the pass and the reduction of its partials: the three totals land in c->mon_buf +
+// 3 * c->mon_cap.  phi and f are read where they lie: the level-0 grids, or the caller's arrays
+// of a device-bound problem (pitch N, double).  omega > 0: the damping pass (what includes the
+// residual), which writes phi there too, and the scatter of its deferred outputs.
+template <class T>
+static int mon_enqueue(pgmg_ctx *c, unsigned what, double omega = 0.0)
+{
+    const Level &L = c->lv[0];
+    const MonGrid mg = mon_grid(L.N, L.lo, L.hi);
+    const int np = mg.tiles * mg.bands;
+    const bool damp = omega > 0.0;
+    PGMG_TRY(mon_reserve(c, np, damp ? mon_side_elems(L.N, mg) * sizeof(T) : 0));
     const bool res = (what & kMonRes) != 0;
     const bool gen = res && c->ext_f == nullptr && c->gen_rhs;
     const unsigned mode = what | (gen ? kMonGen : 0u) | (damp ? kMonDamp : 0u);
@@ -386,17 +496,9 @@ static int mon_enqueue(pgmg_ctx *c, unsigned what, double omega = 0.0)
         // omega * 0.25 * (h0 * h0) in double, left to right, then the element type
         a.w = (T)(omega * 0.25 * (L.h * L.h));
     };
-    // the deferred outputs into phi: ~4 columns per thread of a row, ~16 rows per thread of a
-    // tile boundary
     auto scatter = [&](auto *x, long long Px) {
         using SX = std::remove_pointer_t<decltype(x)>;
-        const int bxr = std::max(1, (L.N + 4 * kBlock - 1) / (4 * kBlock));
-        const int bxc = std::max(1, (L.N + 16 * kBlock - 1) / (16 * kBlock));
-        k_mon_scatter_rows<T, SX><<<dim3(bxr, 2 * mg.bands), dim3(kBlock), 0, c->s>>>(
-            x, Px, sr, L.N, L.lo, L.hi, L.u0, L.u1, mg.bands);
-        if (mg.tiles > 1)
-            k_mon_scatter_cols<T, SX><<<dim3(bxc, mg.tiles - 1), dim3(kBlock), 0, c->s>>>(
-                x, Px, sc, L.N, L.u0, L.u1);
+        mon_scatter<T, SX>(x, Px, sr, sc, L.N, L.lo, L.hi, L.u0, L.u1, mg, c->s);
     };
     if (c->ext_phi == nullptr) {
         MonArgsT<T, T, T> a{};
@@ -445,8 +547,7 @@ static int mon_check(pgmg_ctx *c, unsigned what)
 // omega of the damping entries, and what they cannot run on
 static int damp_check(pgmg_ctx *c, double omega, const char *who)
 {
-    if (!std::isfinite(omega) || omega <= 0.0 || omega > 1.0)
-        return set_err(PGMG_ERR_ARG, std::string(who) + ": omega must be in (0, 1]");
+    PGMG_TRY(damp_omega_check(omega, who));
     if (c->cfg.world > 1)
         return set_err(PGMG_ERR_STATE, std::string(who) + ": one GPU only (world 1); row strips "
                                                           "are not supported");

@@ -34,6 +34,8 @@ struct OpScratch {
     size_t tmp_elems = 0;
     double *side = nullptr;   // the in-place passes' deferred tile-edge outputs
     size_t side_elems = 0;
+    double *mon = nullptr;    // pgmg_damp_grid: 3 partial sums per workgroup, then the 3 totals
+    size_t mon_elems = 0;
 };
 
 // One scratch set per stream: ops enqueued on different streams never share partial sums,
@@ -81,9 +83,53 @@ int ensure_side(hipStream_t s, OpScratch &o, size_t elems)
     return PGMG_OK;
 }
 
+int ensure_mon(hipStream_t s, OpScratch &o, size_t elems)
+{
+    std::lock_guard<std::mutex> lk(g_op_mu);
+    if (elems <= o.mon_elems) return PGMG_OK;
+    if (o.mon) {
+        HIPC(hipStreamSynchronize(s));
+        HIPC(hipFree(o.mon));
+    }
+    o.mon = nullptr;
+    o.mon_elems = 0;
+    HIPC(hipMalloc((void **)&o.mon, elems * sizeof(double)));
+    o.mon_elems = elems;
+    return PGMG_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+// One damping pass x <- x + w r on the caller's arrays (pitch N): the level-general launch of
+// the context's damping pass (pgmg_monitor.hip), its decomposition and sums those of a context
+// of that N.
+int pgmg_damp_grid(double *d_x, const double *d_f, int N, double h, double omega, double *res_norm,
+                   void *stream)
+{
+    if (!d_x || !d_f || N < 5 || ((N - 1) & (N - 2)) != 0 || !std::isfinite(h) || !(h > 0.0))
+        return set_err(PGMG_ERR_ARG, "pgmg_damp_grid: need x, f, N = 2^k + 1 with k >= 2, h > 0");
+    int e = damp_omega_check(omega, "pgmg_damp_grid");
+    if (e) return e;
+    hipStream_t s = (hipStream_t)stream;
+    OpScratch *op = nullptr;
+    if ((e = ensure_scratch(s, 0, &op))) return e;
+    const size_t np = (size_t)damp_grid_blocks(N);
+    if ((e = ensure_side(s, *op, damp_grid_side_elems(N)))) return e;
+    if ((e = ensure_mon(s, *op, 3 * np + 3))) return e;
+    double *sums = res_norm ? op->mon + 3 * np : nullptr;
+    launch_damp_grid<double>(d_x, N, d_f, N, N, 1.0 / (h * h), h, omega, nullptr, nullptr, op->mon,
+                             op->side, sums, s);
+    HIPC(hipGetLastError());
+    if (res_norm) {
+        double t[3];
+        HIPC(hipMemcpyAsync(t, sums, sizeof(t), hipMemcpyDeviceToHost, s));
+        HIPC(hipStreamSynchronize(s));
+        *res_norm = std::sqrt(t[0]);
+    }
+    return PGMG_OK;
+}
 
 int pgmg_jacobi(double *d_x, double *d_tmp, const double *d_f, int H, int W, double h, int v,
                 double eps, int *sweeps_done, void *stream)
@@ -254,7 +300,7 @@ int pgmg_ops_release(void *stream)
     }
     HIPC(hipStreamSynchronize(s));   // ops still queued on s may use the set
     for (void *p : {(void *)o.partials, (void *)o.flags, (void *)o.stats, (void *)o.scalar,
-                    (void *)o.tmp, (void *)o.side})
+                    (void *)o.tmp, (void *)o.side, (void *)o.mon})
         if (p) HIPC(hipFree(p));
     return PGMG_OK;
 }
