@@ -481,6 +481,40 @@ int pgmg_fmg(pgmg_ctx *ctx, int nu);
  * history.  f is left untouched.  The damping pass's side buffer is allocated on the first
  * call. */
 int pgmg_fmg_damped(pgmg_ctx *ctx, int nu, double omega);
+/* ---- Full multigrid with Dirichlet data -------------------------------------------------
+ * pgmg_fmg and pgmg_fmg_damped start from u_L = 0 and end with a zero boundary: a problem whose
+ * phi carries boundary data gets the answer to another problem.  pgmg_fmg_bc(ctx, nu, omega)
+ * is the same climb with the boundary the caller set.  Let g be the frame of the CURRENT phi at
+ * the time of the call: rows 0 and N-1 and columns 0 and N-1 of level 0 (the context's phi, or
+ * the caller's device array of pgmg_set_problem_device, in the context's element type).  The
+ * levels, h_l and the restricted f chain (step 1) are pgmg_fmg's; the frame of level l is the
+ * injection of g, g_l(j, i) = g(2^l j, 2^l i) on the frame points of the N_l x N_l grid; the
+ * interior of phi is ignored.
+ *   2. u_L = 0 on the interior and g_L on the frame, then nu x v_cycle(u_L, f_L, N_L, h_L).
+ *   3. for l = L-1 .. 0: u_l = C(u_{l+1}), the same cubic interpolation, frame included; the
+ *      frame of u_l is then overwritten with g_l (the interpolated frame differs from it by
+ *      O(h^4); the caller's data is exact); then
+ *      nu x { v_cycle(u_l, f_l, N_l, h_l);  if omega > 0: u_l <- damp(u_l, f_l, h_l, omega) }.
+ *   phi is overwritten with u_0, whose frame is bit for bit g; f is left untouched.
+ * omega == 0.0 is the undamped climb of pgmg_fmg, omega in (0, 1] adds pgmg_fmg_damped's damping
+ * pass (the same formula, the boundary never written; the coarsest level is not damped); any
+ * other omega (not finite, < 0 or > 1): PGMG_ERR_ARG.  With a frame of +0.0 everywhere phi and
+ * the statistics are bitwise those of pgmg_fmg (omega == 0) or pgmg_fmg_damped.  A non-finite
+ * frame value is no error: it propagates, as it does through the cycles.  On the analytic
+ * problem with non-integer p, q and the exact solution's frame, nu = 2 lands at 0.92 - 1.0 x the
+ * discretisation error (tests/test_fmg_bc_cpu.py), where the zero-frame climb is orders of
+ * magnitude above it.  The model is tests/fmg_bc_model.py.
+ * Everything else is pgmg_fmg's contract: nu < 1, n_coarse < 5 (N_L = 3) or a null context:
+ * PGMG_ERR_ARG; before pgmg_set_problem*: PGMG_ERR_STATE; world > 1: PGMG_ERR_STATE; all before
+ * anything is enqueued.  fp64 and fp32; problems set with pgmg_set_problem and
+ * pgmg_set_problem_device (the caller's phi is staged into the context's grids first, g is taken
+ * from there, the result is copied out: synchronous; asynchronous on the context's stream
+ * otherwise).  Every early-exit check is decided in-stream; the sweep and early-exit statistics
+ * continue and are the model's.  It drops the carry and resets the speculation history.  A later
+ * pgmg_vcycle / pgmg_wcycle / pgmg_solve continues from u_0 and keeps its frame.  The frame
+ * buffer (4 N elements) is allocated on the first call.  Cost over pgmg_fmg: the frame's save, a
+ * fill of the coarsest grid and one to five launches of O(N_l) elements per level. */
+int pgmg_fmg_bc(pgmg_ctx *ctx, int nu, double omega);
 /* Measurement: `reps` cubic interpolation passes level 1 -> level 0 back to back on the
  * context's stream between two hipEvents, after two warm ones; mean device ms per pass and its
  * algorithmic bytes (one element per fine point written + one per coarse point read).  Needs

@@ -230,11 +230,12 @@ class Solver:
     def fcycle(self, n=1):
         check(self.lib.pgmg_fcycle(self.h, int(n)), "pgmg_fcycle")
 
-    def fmg(self, nu=2, damp=None):
+    def fmg(self, nu=2, damp=None, boundary="zero"):
         """Replace phi with the full-multigrid solution of the problem's own right-hand side
         (pgmg_fmg): f restricted down the pyramid, the coarsest level solved from zero, then per
-        level the cubic interpolation of the coarser solution and `nu` V-cycles.  The current
-        phi is ignored.  With nu=2 the result is at the discretisation error for about 8/3
+        level the cubic interpolation of the coarser solution and `nu` V-cycles.  With
+        boundary="zero" the current phi is ignored, boundary included; with "keep" its interior
+        is ignored.  With nu=2 the result is at the discretisation error for about 8/3
         finest-level V-cycles of work, so a solve that starts from it needs few cycles::
 
             s.set_problem(None, f); s.fmg(); s.solve(rtol=1e-8)
@@ -242,8 +243,17 @@ class Solver:
         damp: None is pgmg_fmg exactly; an omega in (0, 1] (0.5 recommended) follows every
         V-cycle of the climb with a damping pass on that level (pgmg_fmg_damped), which removes
         the checkerboard error the undamped smoother leaves: for any right-hand side but the
-        smooth analytic one the residual is about 100 times smaller.  One GPU only."""
-        if damp is None:
+        smooth analytic one the residual is about 100 times smaller.
+        boundary: "zero" solves the problem with a zero Dirichlet boundary and leaves phi with
+        one, whatever phi held; "keep" (pgmg_fmg_bc) solves the problem whose Dirichlet data is
+        the frame of the current phi (rows and columns 0 and N-1): every level of the climb
+        carries the injection of that frame, and the result's frame is bit for bit the one phi
+        had.  With an all-zero frame the two give the same bits.  One GPU only."""
+        if boundary not in ("zero", "keep"):
+            raise ValueError(f"boundary must be 'zero' or 'keep', not {boundary!r}")
+        if boundary == "keep":
+            check(self.lib.pgmg_fmg_bc(self.h, int(nu), float(damp or 0.0)), "pgmg_fmg_bc")
+        elif damp is None:
             check(self.lib.pgmg_fmg(self.h, int(nu)), "pgmg_fmg")
         else:
             check(self.lib.pgmg_fmg_damped(self.h, int(nu), float(damp)), "pgmg_fmg_damped")
@@ -324,7 +334,8 @@ class Solver:
         return ms.value, b.value
 
     def solve(self, cycle="V", rtol=1e-3, atol=0.0, max_cycles=30, check_every=1,
-              stall_ratio=0.0, stall_checks=2, error=False, damp=0.0, start=None, nu=2):
+              stall_ratio=0.0, stall_checks=2, error=False, damp=0.0, start=None, nu=2,
+              boundary="zero"):
         """Cycle until the residual norm is at most max(atol, rtol * r0), the cycle cap, a
         stall or a non-finite norm (pgmg_solve; the stop rule: include/pgmg.h).  Returns the
         PgmgSolveInfo with a `.history` list of (cycle, res, rel_error), check 0 first.
@@ -335,11 +346,14 @@ class Solver:
         (damped when damp is positive), so check 0 -- and r0 of the rule -- is the FMG iterate's
         and info.cycles counts the cycles after it.  rtol is then relative to a residual FMG has
         already brought down (by ~1e-3 with damp=0.5): give the target as atol to compare with
-        a solve from zero."""
+        a solve from zero.
+        boundary: passed to fmg with start="fmg": "zero" ignores the current phi, boundary
+        included, and solves the zero-boundary problem; "keep" ignores its interior only and
+        solves the problem with the Dirichlet data phi carries (ignored without start)."""
         if start not in (None, "fmg"):
             raise ValueError(f"start must be None or 'fmg', not {start!r}")
         if start == "fmg":
-            self.fmg(nu, damp if damp != 0.0 else None)
+            self.fmg(nu, damp if damp != 0.0 else None, boundary)
         o = PgmgSolveOpts()
         check(self.lib.pgmg_solve_opts_default(C.byref(o)), "pgmg_solve_opts_default")
         kinds = {"V": PGMG_CYCLE_V, "W": PGMG_CYCLE_W, "F": PGMG_CYCLE_F}

@@ -147,6 +147,7 @@ SIGNATURES = [
     ("pgmg_damp_time", C.c_int, [_P, C.c_double, C.c_int, _DP, _DP]),
     ("pgmg_fmg", C.c_int, [_P, C.c_int]),
     ("pgmg_fmg_damped", C.c_int, [_P, C.c_int, C.c_double]),
+    ("pgmg_fmg_bc", C.c_int, [_P, C.c_int, C.c_double]),
     ("pgmg_fmg_interp_time", C.c_int, [_P, C.c_int, _DP, _DP]),
     ("pgmg_stats", C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     ("pgmg_stats_detail", C.c_int, [_P, C.POINTER(C.c_longlong)]),

@@ -246,6 +246,10 @@ struct pgmg_ctx {
     // levels below the tail's top (l > nb; the others use lv[l].A)
     std::vector<pgmg::Level> fmg_lv;
     std::vector<pgmg::Grid> fmg_F, fmg_U;
+    // pgmg_fmg_bc, allocated on its first call (a registered allocation): the frame of level-0
+    // phi at the time of the call, 4 N elements of the context's type -- row 0, row N-1,
+    // column 0, column N-1
+    void *fmg_frame = nullptr;
 };
 
 namespace pgmg {

@@ -127,6 +127,10 @@ int pgmg_destroy(pgmg_ctx *c)
     for (auto &g : c->Ffmg_l) free_grid(g);
     for (auto &g : c->fmg_F) free_grid(g);
     for (auto &g : c->fmg_U) free_grid(g);
+    if (c->fmg_frame) {
+        unregister_alloc(c->fmg_frame);
+        (void)hipFree(c->fmg_frame);
+    }
     if (c->fmg_tab) (void)hipFree(c->fmg_tab);
     if (c->flags) (void)hipFree(c->flags);
     if (c->stats) (void)hipFree(c->stats);

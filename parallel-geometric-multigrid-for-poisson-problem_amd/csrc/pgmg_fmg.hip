@@ -10,7 +10,9 @@
 // LDS tail (one launch per level at or below the tail's top, that level as its top) and
 // enqueue_cycle from a bulk level with the level's restricted f standing in for lv[l].F.
 // pgmg_fmg_damped is the same climb with the damping pass (pgmg_monitor.hip, fmg_damp_level)
-// after every V-cycle of it, on that level's grids.
+// after every V-cycle of it, on that level's grids.  pgmg_fmg_bc is either climb with the frame
+// of the current phi carried down the pyramid by injection (k_frame_save, k_frame_inject) and
+// put back on every level after the interpolation, beside the passes, not inside them.
 #include <algorithm>
 #include <string>
 #include <utility>
@@ -199,6 +201,72 @@ static int launch_interp_cubic(const T *coarse, int Nc, int Pc, T *fine, int Pf,
     return PGMG_OK;
 }
 
+// pgmg_fmg_bc: the frame g of level-0 phi (rows 0 and N-1, columns 0 and N-1) is saved into the
+// context's frame buffer -- top row, bottom row, left column, right column, N elements each --
+// before anything of the call writes level 0, and injected into a level's grids from there:
+// g_l(j, i) = g(stride j, stride i), stride = 2^l.  A corner is one element of g, stored in a
+// row line and in a column line: both writers of a corner write the same value.
+template <class T>
+__global__ void k_frame_save(const T *src, long long P, int N, T *frame)
+{
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < 4 * N; k += gridDim.x * blockDim.x) {
+        const int q = k % N, w = k / N;
+        const int j = w == 0 ? 0 : (w == 1 ? N - 1 : q);
+        const int i = w < 2 ? q : (w == 2 ? 0 : N - 1);
+        frame[k] = src[(long long)j * P + i];
+    }
+}
+
+// the four frame lines of an Nl x Nl level grid from the buffer of the (Nl - 1) stride + 1
+// points per side of level 0 (the column stores are pitch-strided: 4 Nl elements a level)
+template <class T>
+__global__ void k_frame_inject(T *dst, long long P, int Nl, const T *frame, int stride)
+{
+    const long long N = (long long)(Nl - 1) * stride + 1;
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < 4 * Nl; k += gridDim.x * blockDim.x) {
+        const int q = k % Nl, w = k / Nl;
+        const int j = w == 0 ? 0 : (w == 1 ? Nl - 1 : q);
+        const int i = w < 2 ? q : (w == 2 ? 0 : Nl - 1);
+        dst[(long long)j * P + i] = frame[w * N + (long long)q * stride];
+    }
+}
+
+// the frame buffer, 4 N elements of the context's type (allocated on the first pgmg_fmg_bc)
+static int fmg_frame_reserve(pgmg_ctx *c)
+{
+    if (c->fmg_frame) return PGMG_OK;
+    const size_t bytes = (size_t)4 * c->cfg.N * c->lv[0].es;
+    if (hipMalloc(&c->fmg_frame, bytes) != hipSuccess) {
+        c->fmg_frame = nullptr;
+        return set_err(PGMG_ERR_NOMEM, "hipMalloc failed for pgmg_fmg_bc's frame buffer");
+    }
+    register_alloc(c->fmg_frame, bytes);
+    return PGMG_OK;
+}
+
+template <class T>
+static int launch_frame_save(pgmg_ctx *c, const T *src, int P, int N)
+{
+    T *frame = static_cast<T *>(c->fmg_frame);
+    PGMG_TRY(check_span(src, P, (int)sizeof(T), 0, N - 1, 0, N - 1, "k_frame_save phi"));
+    PGMG_TRY(check_span(frame, 0, (int)sizeof(T), 0, 0, 0, 4LL * N - 1, "k_frame_save frame"));
+    k_frame_save<T><<<dim3((4 * N + 255) / 256), dim3(256), 0, c->s>>>(src, P, N, frame);
+    return PGMG_OK;
+}
+
+// level l's frame g_l into one of its grids (N_0 = (Nl - 1) 2^l + 1: the buffer's line length)
+template <class T>
+static int launch_frame_inject(pgmg_ctx *c, T *dst, int P, int Nl, int l)
+{
+    const T *frame = static_cast<const T *>(c->fmg_frame);
+    const long long N = (long long)(Nl - 1) * (1LL << l) + 1;
+    if (N != c->cfg.N) return set_err(PGMG_ERR_STATE, "k_frame_inject: not a level of this context");
+    PGMG_TRY(check_span(dst, P, (int)sizeof(T), 0, Nl - 1, 0, Nl - 1, "k_frame_inject grid"));
+    PGMG_TRY(check_span(frame, 0, (int)sizeof(T), 0, 0, 0, 4 * N - 1, "k_frame_inject frame"));
+    k_frame_inject<T><<<dim3((4 * Nl + 255) / 256), dim3(256), 0, c->s>>>(dst, P, Nl, frame, 1 << l);
+    return PGMG_OK;
+}
+
 // FMG level l of the context: levels 0 .. nb are the context's own (bulk levels and the tail's
 // top), the ones below continue the halving down to the first N <= n_coarse
 static int fmg_setup(pgmg_ctx *c)
@@ -256,12 +324,18 @@ struct FmgLevelF {
 };
 
 // omega > 0 (pgmg_fmg_damped): one damping pass after every V-cycle of the climb
+// bc (pgmg_fmg_bc): every u_l carries the frame g_l of the current phi instead of a zero one
 template <class T>
-static int fmg_enqueue(pgmg_ctx *c, int nu, double omega)
+static int fmg_enqueue(pgmg_ctx *c, int nu, double omega, bool bc)
 {
     const bool damped = omega > 0.0;
     const int nb = c->nb, Lc = (int)c->fmg_lv.size() - 1;
     const std::vector<Level> &lv = c->fmg_lv;
+    // 0. g, before the last interpolation (or, at Lc = 0, the coarsest start) overwrites it
+    if (bc) PGMG_TRY(launch_frame_save(c, G<T>(c->lv[0].A), lv[0].P, lv[0].N));
+    auto inject = [&](const Grid &g, int l) -> int {
+        return launch_frame_inject(c, G<T>(g), lv[l].P, lv[l].N, l);
+    };
     // 1. the f chain, level by level (every level's values are used)
     for (int l = 0; l < Lc; ++l)
         launch_restrict_values(G<T>(fmg_f(c, l)), lv[l].N, lv[l].P, G<T>(c->fmg_F[l + 1]), lv[l + 1].N,
@@ -280,12 +354,30 @@ static int fmg_enqueue(pgmg_ctx *c, int nu, double omega)
         HIPC(launch_tail_gamma(t, 1, c->s));
         return PGMG_OK;
     };
-    // 2. the coarsest level from zero (the tail starts from zero in LDS and stores every point)
-    PGMG_TRY(tail_level(Lc, false, nu));
+    // 2. the coarsest level from zero (the tail starts from zero in LDS and stores every point);
+    // with a frame: from the zeroed grid with g_L injected, read from global memory
+    if (bc) {
+        const Grid &u = fmg_u(c, Lc);
+        PGMG_TRY(check_span(G<T>(u), lv[Lc].P, (int)sizeof(T), 0, lv[Lc].N - 1, 0, lv[Lc].P - 1,
+                            "pgmg_fmg_bc coarsest grid"));
+        launch_fill_rows(G<T>(u), lv[Lc].P, 0, lv[Lc].N, c->s);
+        PGMG_TRY(inject(u, Lc));
+    }
+    PGMG_TRY(tail_level(Lc, bc, nu));
     // 3. the climb
     for (int l = Lc - 1; l >= 0; --l) {
         PGMG_TRY(launch_interp_cubic(G<T>(fmg_u(c, l + 1)), lv[l + 1].N, lv[l + 1].P,
                                      G<T>(fmg_u(c, l)), lv[l].P, c->s));
+        if (bc) {
+            // the interpolated frame is g_l + O(h^4): the caller's data goes back bitwise
+            PGMG_TRY(inject(fmg_u(c, l), l));
+            // level l + 1 is a child from here on, entered from zero: the frames of its error
+            // grids are zero again (a tail top is stored whole by its first visit)
+            if (l + 1 < nb) {
+                launch_zero_frame(G<T>(c->lv[l + 1].A), lv[l + 1].P, lv[l + 1].N, c->s);
+                launch_zero_frame(G<T>(c->lv[l + 1].B), lv[l + 1].P, lv[l + 1].N, c->s);
+            }
+        }
         const bool gen = l == 0 && c->rgfx != nullptr;   // level 0's analytic f: regenerated
         if (l >= nb) {
             if (!damped) {
@@ -299,10 +391,16 @@ static int fmg_enqueue(pgmg_ctx *c, int nu, double omega)
             }
             continue;
         }
-        // u_l has a zero boundary (u_L = 0 and C keeps it): the level's other grids mirror it
+        // u_l has a zero boundary (u_L = 0 and C keeps it), or g_l: the level's other grids (the
+        // ping-pong buffer; at level 0 the cross-fused cycles rotate through S too) mirror it
         Level &L = c->lv[l];
-        launch_zero_frame(G<T>(L.B), L.P, L.N, c->s);
-        if (l == 0 && c->S.base) launch_zero_frame(G<T>(c->S), L.P, L.N, c->s);
+        if (bc) {
+            PGMG_TRY(inject(L.B, l));
+            if (l == 0 && c->S.base) PGMG_TRY(inject(c->S, 0));
+        } else {
+            launch_zero_frame(G<T>(L.B), L.P, L.N, c->s);
+            if (l == 0 && c->S.base) launch_zero_frame(G<T>(c->S), L.P, L.N, c->s);
+        }
         const FmgLevelF stand_in(c, l);
         // the damp of what a cycle left: every cycle ends with its iterate under lv[l].A, but
         // which grid that is may change (the cross-fused cycles swap the roles of A / B / S), so
@@ -332,8 +430,8 @@ static int fmg_enqueue(pgmg_ctx *c, int nu, double omega)
     return PGMG_OK;
 }
 
-// pgmg_fmg (omega = 0) and pgmg_fmg_damped
-static int fmg_run(pgmg_ctx *c, int nu, double omega, const char *who_)
+// pgmg_fmg (omega = 0), pgmg_fmg_damped and, with bc, pgmg_fmg_bc
+static int fmg_run(pgmg_ctx *c, int nu, double omega, const char *who_, bool bc = false)
 {
     const std::string who(who_);
     if (!c) return set_err(PGMG_ERR_ARG, "null ctx");
@@ -349,6 +447,7 @@ static int fmg_run(pgmg_ctx *c, int nu, double omega, const char *who_)
     // the damping pass's side buffer and partials, sized for level 0 (the largest) before
     // anything is enqueued
     if (omega != 0.0) PGMG_TRY(fmg_damp_reserve(c, c->cfg.N));
+    if (bc) PGMG_TRY(fmg_frame_reserve(c));
     // an entry that changes phi: the carry goes, the speculation starts over (the statistics
     // continue)
     c->carry = false;
@@ -359,7 +458,7 @@ static int fmg_run(pgmg_ctx *c, int nu, double omega, const char *who_)
     const bool ext = c->ext_phi != nullptr;
     if (ext) PGMG_TRY(ext_stage_in(c, false));
     HIPC(hipEventRecord(c->ev0, c->s));
-    PGMG_TRY(c->fp32 ? fmg_enqueue<float>(c, nu, omega) : fmg_enqueue<double>(c, nu, omega));
+    PGMG_TRY(c->fp32 ? fmg_enqueue<float>(c, nu, omega, bc) : fmg_enqueue<double>(c, nu, omega, bc));
     HIPC(hipGetLastError());
     HIPC(hipEventRecord(c->ev1, c->s));
     if (ext) {
@@ -380,6 +479,12 @@ int pgmg_fmg_damped(pgmg_ctx *c, int nu, double omega)
     // (omega = 0 is no damped call: refused here, fmg_run reads it as pgmg_fmg)
     if (omega == 0.0) return damp_omega_check(omega, "pgmg_fmg_damped");
     return fmg_run(c, nu, omega, "pgmg_fmg_damped");
+}
+
+int pgmg_fmg_bc(pgmg_ctx *c, int nu, double omega)
+{
+    // (omega = 0: the undamped climb; fmg_run checks any other value)
+    return fmg_run(c, nu, omega, "pgmg_fmg_bc", true);
 }
 
 int pgmg_fmg_interp_time(pgmg_ctx *c, int reps, double *ms_per_pass, double *bytes)
