@@ -6,7 +6,6 @@
 #include <cstdio>
 #include <string>
 #include <utility>
-#include <vector>
 
 #include "pgmg_host.h"
 #include "pgmg_coarse.h"
@@ -107,15 +106,35 @@ static int timed_end(pgmg_ctx *c, int slot, int idx)
     return PGMG_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Level geometry and the fused passes' argument blocks.  strip_rows alone derives a pass's rows
+// from a level; pre_args / post_args fill what follows from the context and the level, whoever
+// launches the pass the rest: iterates, pin_ec, fired, cond, Px / Po, sw_adj, extended post rows.
+// ---------------------------------------------------------------------------
+StripRows pgmg::strip_rows(const Level &L, const Level &C)
+{
+    StripRows r;
+    r.jc0 = L.lo / 2;
+    r.jc1 = (L.hi < L.N ? L.hi : L.N - 1) / 2;
+    r.row_lo = L.u0;
+    r.row_hi = L.u1;
+    // coarse rows this rank restricts into (its strip's rows; the fix-up honours them too)
+    r.rc_lo = r.jc0 > 1 ? r.jc0 : 1;
+    r.rc_hi = r.jc1 < C.N - 1 ? r.jc1 : C.N - 1;
+    r.x_lo = L.u0 - 4 > 1 ? L.u0 - 4 : 1;
+    r.x_hi = L.u1 + 4 < L.N - 1 ? L.u1 + 4 : L.N - 1;
+    return r;
+}
+
 PostRows pgmg::post_rows(const pgmg_ctx *c, int l)
 {
     const Level &L = c->lv[l];
-    PostRows r{L.lo / 2, (L.hi < L.N ? L.hi : L.N - 1) / 2, L.u0, L.u1};
     if (l > 0 && is_dist(c, l)) {
         const int r0 = std::max(L.lo - kPostExt, 0), r1 = std::min(L.hi + kPostExt, L.N - 1);
-        r = {r0 / 2, r1 / 2, std::max(r0, 1), r1};
+        return {r0 / 2, r1 / 2, std::max(r0, 1), r1};
     }
-    return r;
+    const StripRows sr = strip_rows(L, c->lv[l + 1]);
+    return {sr.jc0, sr.jc1, sr.row_lo, sr.row_hi};
 }
 
 int pgmg::tile_np(const pgmg_ctx *c, int l, bool post)
@@ -123,14 +142,59 @@ int pgmg::tile_np(const pgmg_ctx *c, int l, bool post)
     if (l < 1 || l >= c->nb) return 0;
     const Level &L = c->lv[l];
     if (!coarse_tile_ok(L.N, is_dist(c, l))) return 0;
-    const int Nc = c->lv[l + 1].N;
-    int jc0 = L.lo / 2, jc1 = (L.hi < L.N ? L.hi : L.N - 1) / 2;
-    if (post) {
-        const PostRows pr = post_rows(c, l);
-        jc0 = pr.jc0;
-        jc1 = pr.jc1;
-    }
-    return coarse_tile_blocks_rows(L.N, std::max(jc0, 1), std::min(jc1, Nc - 1));
+    const StripRows sr = strip_rows(L, c->lv[l + 1]);
+    const PostRows pr = post_rows(c, l);
+    return post ? coarse_tile_blocks_rows(L.N, std::max(pr.jc0, 1), std::min(pr.jc1, c->lv[l + 1].N - 1))
+                : coarse_tile_blocks_rows(L.N, sr.rc_lo, sr.rc_hi);
+}
+
+// level 0 with an analytic RHS, or the F climb's current level: regenerate f in-kernel
+static const double *gen_table(const pgmg_ctx *c, int l, const double *fine, const double *climb)
+{
+    return l == 0 ? fine : (l == c->call.gen_level ? climb : nullptr);
+}
+
+template <class T>
+static PreArgsT<T> pre_args(const pgmg_ctx *c, int l)
+{
+    const Level &L = c->lv[l], &C = c->lv[l + 1];
+    PreArgsT<T> pa{};
+    pa.f = G<T>(L.F);
+    pa.rc = G<T>(C.F);
+    pa.partials = c->partials;
+    pa.stats = c->stats;
+    const StripRows sr = pass_geometry(pa, L, C);
+    pa.rc_lo = sr.rc_lo;
+    pa.rc_hi = sr.rc_hi;
+    pa.gfx = gen_table(c, l, c->rgfx, c->call.lgfx);
+    pa.gsy = gen_table(c, l, c->rgsy, c->call.lgsy);
+    return pa;
+}
+
+template <class T>
+static PostArgsT<T> post_args(const pgmg_ctx *c, int l)
+{
+    const Level &L = c->lv[l], &C = c->lv[l + 1];
+    PostArgsT<T> po{};
+    po.ec = G<T>(C.A);
+    po.f = G<T>(L.F);
+    po.partials = c->partials;
+    po.stats = c->stats;
+    pass_geometry(po, L, C);
+    po.gfx = gen_table(c, l, c->rgfx, c->call.lgfx);
+    po.gsy = gen_table(c, l, c->rgsy, c->call.lgsy);
+    return po;
+}
+
+// the fix-up / rare-path block of a check with np partials, decided from the shared partials
+static FixArgsF fix_args(const pgmg_ctx *c, int np)
+{
+    FixArgsF fa{};
+    fa.partials = c->partials;
+    fa.np = np;
+    fa.eps = c->cfg.eps;
+    fa.stats = c->stats;
+    return fa;
 }
 
 template <class T> static int enqueue_children(pgmg_ctx *c, int l, int gamma);
@@ -147,10 +211,7 @@ static int enqueue_smooth_t(pgmg_ctx *c, int l, int which, int v, bool x0_zero)
     for (int k = 1; k <= S; ++k) {
         T *in = G<T>((k & 1) ? L.A : L.B);
         T *out = G<T>((k & 1) ? L.B : L.A);
-        if (is_dist(c, l) && !(k == 1 && x0_zero)) {
-            int e = c->comm->halo((k & 1) ? L.A : L.B, L, 1, c->s);
-            if (e) return e;
-        }
+        if (is_dist(c, l) && !(k == 1 && x0_zero)) PGMG_TRY(c->comm->halo((k & 1) ? L.A : L.B, L, 1, c->s));
         SweepArgsT<T> a{};
         a.xin = (k == 1 && x0_zero) ? nullptr : in;
         a.f = G<T>(L.F);
@@ -167,8 +228,7 @@ static int enqueue_smooth_t(pgmg_ctx *c, int l, int which, int v, bool x0_zero)
         a.row1 = L.u1;
         const int ev = (fine && a.partials == nullptr && !(k == 1 && x0_zero)) ? timed_begin(c, 0) : -1;
         launch_sweep(a, k == 1 && x0_zero, l == 0, c->s);
-        int te = timed_end(c, 0, ev);
-        if (te) return te;
+        PGMG_TRY(timed_end(c, 0, ev));
         if (k >= 2) {
             int rpb, gx, gy;
             const int np = sweep_blocks(L.N, L.u0, L.u1, &rpb, &gx, &gy);
@@ -188,8 +248,7 @@ static int enqueue_smooth_t(pgmg_ctx *c, int l, int which, int v, bool x0_zero)
             f.global_sum = nullptr;
             if (is_dist(c, l)) {
                 launch_sum_partials(c->partials, np, c->scalar, c->s);
-                int e = c->comm->allreduce_sum(c->scalar, 1, c->s);
-                if (e) return e;
+                PGMG_TRY(c->comm->allreduce_sum(c->scalar, 1, c->s));
                 f.global_sum = c->scalar;
             }
             launch_fixup(f, c->s);
@@ -232,10 +291,7 @@ static int enqueue_children(pgmg_ctx *c, int l, int gamma)
     // 3^9 times, one launch per visit cost ~8 % of its time in launch overhead
     if (l + 1 == c->nb && gamma > 1 && tuning_int("PGMG_TAIL_VISITS", 1) != 0)
         return enqueue_tail_t<T>(c, gamma, false, gamma);
-    for (int i = 0; i < gamma; ++i) {
-        int e = enqueue_cycle_t<T>(c, l + 1, gamma, i == 0);
-        if (e) return e;
-    }
+    for (int i = 0; i < gamma; ++i) PGMG_TRY(enqueue_cycle_t<T>(c, l + 1, gamma, i == 0));
     return PGMG_OK;
 }
 
@@ -243,9 +299,112 @@ static int enqueue_children(pgmg_ctx *c, int l, int gamma)
 static int global_sum(pgmg_ctx *c, int np, const double **out)
 {
     launch_sum_partials(c->partials, np, c->scalar, c->s);
-    int e = c->comm->allreduce_sum(c->scalar, 1, c->s);
     *out = c->scalar;
-    return e;
+    return c->comm->allreduce_sum(c->scalar, 1, c->s);
+}
+
+// the block of level l's in-stream decision after a pass with np partials: decided from the
+// pass's log slice lp (a speculative call logs the norm) or the shared partials, on row strips
+// from the all-rank sum; a tile pass's rare path reads the same from its own block
+template <class T>
+static int decide_args(pgmg_ctx *c, int l, int np, const double *lp, FixArgsF *fa, CoarseArgsT<T> *tile)
+{
+    *fa = fix_args(c, np);
+    if (lp) fa->partials = lp;
+    if (is_dist(c, l)) PGMG_TRY(global_sum(c, np, &fa->global_sum));
+    if (tile == nullptr) return PGMG_OK;
+    tile->global_sum = fa->global_sum;
+    tile->dec_partials = fa->partials;
+    tile->dec_np = fa->np;
+    tile->eps = fa->eps;
+    return PGMG_OK;
+}
+
+// The two halves of a fused level, each one checked pass: a log slice for the check (mode as
+// chk_mode), the pass in its timed slot (finest level) -- the tile form (tile != nullptr), the
+// one-sweep form (mode 1) or the full one -- and for an in-stream check (mode 2) the rare path,
+// tile or row-marching, decided on strips from the global sum.
+template <class T>
+static int enqueue_pre_half(pgmg_ctx *c, int l, int mode, bool x0_zero, PreArgsT<T> pa,
+                            CoarseArgsT<T> *tile, int np)
+{
+    const bool fine = (l == 0);
+    double *lp = chk_log(c, np, l, mode);
+    if (lp) pa.partials = lp;
+    const int ev = fine ? timed_begin(c, 1) : -1;
+    if (tile) {
+        tile->partials = pa.partials;
+        launch_pre_tile(*tile, mode == 1 ? 1 : 0, c->s);
+        HIPC(hipGetLastError());
+    } else {
+        PGMG_TRY(mode == 1 ? launch_pre1(pa, x0_zero, c->s) : launch_pre(pa, x0_zero, fine, c->s));
+    }
+    PGMG_TRY(timed_end(c, 1, ev));
+    if (mode != 2) return PGMG_OK;
+    FixArgsF fa;
+    PGMG_TRY(decide_args(c, l, np, lp, &fa, tile));
+    if (tile) {
+        launch_pre_tile(*tile, 2, c->s);
+        HIPC(hipGetLastError());
+        return PGMG_OK;
+    }
+    return launch_pre_rare(fa, pa, x0_zero, c->s);
+}
+
+// r2 (mode 0 only): the finest k_post that also restricts its result to level 2 (k_post_r2)
+template <class T>
+static int enqueue_post_half(pgmg_ctx *c, int l, int mode, PostArgsT<T> po, CoarseArgsT<T> *tile,
+                             int np, bool r2)
+{
+    const bool fine = (l == 0);
+    double *lp = chk_log(c, np, l, mode);
+    if (lp) po.partials = lp;
+    const int ev = fine ? timed_begin(c, 2) : -1;
+    if (r2) {
+        po.r2out = G<T>(c->lv[2].A);
+        po.Pr2 = c->lv[2].P;
+        po.Nr2 = c->lv[2].N;
+        PGMG_TRY(launch_post_r2(po, c->s));
+        c->call.fr2_made = true;
+    } else if (tile) {
+        tile->partials = po.partials;
+        launch_post_tile(*tile, mode == 1 ? 1 : 0, c->s);
+        HIPC(hipGetLastError());
+    } else {
+        PGMG_TRY(mode == 1 ? launch_post1(po, c->s) : launch_post(po, fine, c->s));
+    }
+    PGMG_TRY(timed_end(c, 2, ev));
+    if (mode != 2) return PGMG_OK;
+    FixArgsF fa;
+    PGMG_TRY(decide_args(c, l, np, lp, &fa, tile));
+    if (tile) {
+        launch_post_tile(*tile, 2, c->s);
+        HIPC(hipGetLastError());
+        return PGMG_OK;
+    }
+    return launch_post_rare(fa, po, c->s);
+}
+
+// the tile passes' block of level l (pgmg_coarse.hip); its rows (k_pre's, then k_post's): the caller's
+template <class T>
+static CoarseArgsT<T> tile_args(const pgmg_ctx *c, int l, unsigned *fired)
+{
+    const Level &L = c->lv[l], &C = c->lv[l + 1];
+    CoarseArgsT<T> ca{};
+    ca.f = G<T>(L.F);
+    ca.ec = G<T>(C.A);
+    ca.rc = G<T>(C.F);
+    ca.x2 = G<T>(L.A);
+    ca.stats = c->stats;
+    ca.fired = fired;
+    ca.pre_fired = fired;
+    ca.hh = (T)L.hh;
+    ca.ih = (T)L.ih;
+    ca.N = L.N;
+    ca.P = L.P;
+    ca.Nc = C.N;
+    ca.Pc = C.P;
+    return ca;
 }
 
 // fused level (v1 = v2 = 1): k_pre (+fixup), children, k_post (+fixup)
@@ -263,48 +422,21 @@ static int enqueue_fused_level_t(pgmg_ctx *c, int l, int gamma, bool x0_zero, bo
     // does not store it and k_post recomputes it (x1 = J(0) is pointwise)
     const bool recomp = x0_zero && l > 0 && c->recompute;
     unsigned *fired = smooth_flags(c, l, 0) + (kMaxSweeps - 1);
-    int e;
     // row strips, levels below the finest: k_post also computes kPostExt rows past each
     // strip edge (from deeper halos of f and phi, exchanged with the pre-smooth's anyway),
     // so the parent's prolongation reads this level's correction without an exchange
     const bool ext = dist && l > 0;
     if (dist) {
-        if (!x0_zero && !pin && (e = c->comm->halo(L.A, L, 4, c->s))) return e;
+        if (!x0_zero && !pin) PGMG_TRY(c->comm->halo(L.A, L, 4, c->s));
         // f: 4 rows for k_pre, 3 + kPostExt for the extended k_post (RECOMP reads f 3 rows
         // past its first output row)
-        if (l > 0 && (e = c->comm->halo(L.F, L, 3 + kPostExt, c->s))) return e;
+        if (l > 0) PGMG_TRY(c->comm->halo(L.F, L, 3 + kPostExt, c->s));
     }
-    PreArgsT<T> pa{};
+    PreArgsT<T> pa = pre_args<T>(c, l);
     pa.x0 = G<T>(L.A);
-    pa.f = G<T>(L.F);
     pa.x2 = recomp ? nullptr : G<T>(L.B);
     pa.fired = recomp ? fired : nullptr;
-    pa.rc = G<T>(C.F);
-    pa.partials = c->partials;
-    pa.stats = c->stats;
-    pa.hh = (T)L.hh;
-    pa.ih = (T)L.ih;
-    pa.N = L.N;
-    pa.P = L.P;
-    pa.Nc = C.N;
-    pa.Pc = C.P;
-    pa.jc0 = L.lo / 2;
-    pa.jc1 = (L.hi < L.N ? L.hi : L.N - 1) / 2;
-    pa.row_lo = L.u0;
-    pa.row_hi = L.u1;
-    // coarse rows this rank restricts into (its strip's rows; the fix-up honours them too)
-    pa.rc_lo = pa.jc0 > 1 ? pa.jc0 : 1;
-    pa.rc_hi = pa.jc1 < C.N - 1 ? pa.jc1 : C.N - 1;
-    // level 0 with an analytic RHS, or the F climb's current level: regenerate f in-kernel
-    pa.gfx = l == 0 ? c->rgfx : (l == c->call.gen_level ? c->call.lgfx : nullptr);
-    pa.gsy = l == 0 ? c->rgsy : (l == c->call.gen_level ? c->call.lgsy : nullptr);
     pa.pin_ec = pin ? G<T>(C.A) : nullptr;
-    FixArgsF fa{};
-    fa.partials = c->partials;
-    fa.np = fused_blocks(L.N, pa.jc0, pa.jc1);
-    fa.eps = c->cfg.eps;
-    fa.stats = c->stats;
-    const bool fine = (l == 0);
     // speculative call: record the check (mode 0: no fix-up; 1: predicted to fire, the
     // one-sweep passes; 2: in-stream, logged for its norm)
     int mode = chk_mode(c, l);
@@ -323,76 +455,21 @@ static int enqueue_fused_level_t(pgmg_ctx *c, int l, int gamma, bool x0_zero, bo
     const bool tile = recomp && !pin && pa.gfx == nullptr &&
                       !(c->cfg.flags & PGMG_FLAG_NO_CTILE) && coarse_tile_ok(L.N, dist) &&
                       pa.rc_hi > pa.rc_lo;
-    CoarseArgsT<T> ca{};
-    if (tile) {
-        ca.jt0 = pa.rc_lo;
-        ca.jt1 = pa.rc_hi;
-        ca.own_lo = L.u0;
-        ca.own_hi = L.u1;
-        fa.np = coarse_tile_blocks_rows(L.N, ca.jt0, ca.jt1);
-        ca.f = pa.f;
-        ca.ec = G<T>(C.A);
-        ca.rc = pa.rc;
-        ca.x2 = G<T>(L.A);
-        ca.stats = c->stats;
-        ca.fired = fired;
-        ca.pre_fired = fired;
-        ca.hh = pa.hh;
-        ca.ih = pa.ih;
-        ca.N = L.N;
-        ca.P = L.P;
-        ca.Nc = C.N;
-        ca.Pc = C.P;
-    }
-    double *lp = chk_log(c, fa.np, l, mode);
-    if (lp) pa.partials = lp;
-    int ev = fine ? timed_begin(c, 1) : -1;
-    if (tile) {
-        ca.partials = pa.partials;
-        launch_pre_tile(ca, mode == 1 ? 1 : 0, c->s);
-        HIPC(hipGetLastError());
-    } else if ((e = mode == 1 ? launch_pre1(pa, x0_zero, c->s) : launch_pre(pa, x0_zero, fine, c->s))) {
-        return e;
-    }
-    if ((e = timed_end(c, 1, ev))) return e;
-    if (mode == 2) {
-        if (lp) fa.partials = lp;
-        if (tile) {
-            ca.global_sum = nullptr;
-            if (dist && (e = global_sum(c, fa.np, &ca.global_sum))) return e;
-            ca.dec_partials = fa.partials;
-            ca.dec_np = fa.np;
-            ca.eps = fa.eps;
-            launch_pre_tile(ca, 2, c->s);
-            HIPC(hipGetLastError());
-        } else {
-            if (dist && (e = global_sum(c, fa.np, &fa.global_sum))) return e;
-            if ((e = launch_pre_rare(fa, pa, x0_zero, c->s))) return e;
-        }
-        fa.partials = c->partials;
-    }
-    if ((e = enqueue_children<T>(c, l, gamma))) return e;
+    CoarseArgsT<T> ca = tile_args<T>(c, l, fired);
+    ca.jt0 = pa.rc_lo;
+    ca.jt1 = pa.rc_hi;
+    ca.own_lo = L.u0;
+    ca.own_hi = L.u1;
+    PGMG_TRY(enqueue_pre_half(c, l, mode, x0_zero, pa, tile ? &ca : nullptr,
+                              tile ? tile_np(c, l, false) : fused_blocks(L.N, pa.jc0, pa.jc1)));
+    PGMG_TRY(enqueue_children<T>(c, l, gamma));
     // the correction of level l+1 is not exchanged: a distributed child's k_post computed
     // it kPostExt rows past its strip (a gathered child's is replicated)
-    if (dist && !recomp && (e = c->comm->halo(L.B, L, ext ? 2 + kPostExt : 2, c->s))) return e;
-    PostArgsT<T> po{};
+    if (dist && !recomp) PGMG_TRY(c->comm->halo(L.B, L, ext ? 2 + kPostExt : 2, c->s));
+    PostArgsT<T> po = post_args<T>(c, l);
     po.phi = G<T>(L.B);
     po.pre_fired = recomp ? fired : nullptr;
-    po.ec = G<T>(C.A);
-    po.f = G<T>(L.F);
     po.x2 = G<T>(L.A);
-    po.partials = c->partials;
-    po.stats = c->stats;
-    po.hh = (T)L.hh;
-    po.ih = (T)L.ih;
-    po.N = L.N;
-    po.P = L.P;
-    po.Nc = C.N;
-    po.Pc = C.P;
-    po.jc0 = pa.jc0;
-    po.jc1 = pa.jc1;
-    po.row_lo = L.u0;
-    po.row_hi = L.u1;
     if (ext) {   // rows [lo - kPostExt, hi + kPostExt) written, the strip's rows summed
         const PostRows pr = post_rows(c, l);
         po.jc0 = pr.jc0;
@@ -401,60 +478,23 @@ static int enqueue_fused_level_t(pgmg_ctx *c, int l, int gamma, bool x0_zero, bo
         po.row_hi = pr.row_hi;
         po.sum_lo = L.u0;
         po.sum_hi = L.u1;
-        fa.np = fused_blocks(L.N, po.jc0, po.jc1);
     }
-    po.gfx = pa.gfx;
-    po.gsy = pa.gsy;
-    if (tile) {   // k_post's rows: the strip plus kPostExt rows (dist), its own rows summed
-        ca.jt0 = std::max(po.jc0, 1);
-        ca.jt1 = std::min(po.jc1, C.N - 1);
-        ca.own_lo = po.row_lo;
-        ca.own_hi = po.row_hi;
-        ca.sum_lo = po.sum_hi > po.sum_lo ? po.sum_lo : po.row_lo;
-        ca.sum_hi = po.sum_hi > po.sum_lo ? po.sum_hi : po.row_hi;
-        fa.np = coarse_tile_blocks_rows(L.N, ca.jt0, ca.jt1);
-    }
+    // k_post's tile rows: the strip plus kPostExt rows (dist), its own rows summed
+    ca.jt0 = std::max(po.jc0, 1);
+    ca.jt1 = std::min(po.jc1, C.N - 1);
+    ca.own_lo = po.row_lo;
+    ca.own_hi = po.row_hi;
+    ca.sum_lo = po.sum_hi > po.sum_lo ? po.sum_lo : po.row_lo;
+    ca.sum_hi = po.sum_hi > po.sum_lo ? po.sum_hi : po.row_hi;
     c->call.cur_visit = visit;
     // speculative F-cycle followed by another: the finest k_post also restricts its result to
     // level 2 (the next F-cycle's first restriction step; only when its check is recorded
     // "does not fire", so x2 is the result); its 116-column tiles write more partials
-    const bool r2 = fine && mode == 0 && fr2_want && !dist && !recomp && po.Po == 0 &&
-                    c->nb >= 2 && !is_dist(c, 1) && tuning_int("PGMG_F_R2", 1) != 0;
-    if (r2) fa.np = post_r2_blocks(L.N, po.jc0, po.jc1);
-    lp = chk_log(c, fa.np, l, mode);
-    if (lp) po.partials = lp;
-    ev = fine ? timed_begin(c, 2) : -1;
-    if (r2) {
-        po.r2out = G<T>(c->lv[2].A);
-        po.Pr2 = c->lv[2].P;
-        po.Nr2 = c->lv[2].N;
-        if ((e = launch_post_r2(po, c->s))) return e;
-        c->call.fr2_made = true;
-    } else if (tile) {
-        ca.partials = po.partials;
-        launch_post_tile(ca, mode == 1 ? 1 : 0, c->s);
-        HIPC(hipGetLastError());
-    } else if ((e = mode == 1 ? launch_post1(po, c->s) : launch_post(po, fine, c->s))) {
-        return e;
-    }
-    if ((e = timed_end(c, 2, ev))) return e;
-    if (mode == 2) {
-        if (lp) fa.partials = lp;
-        if (tile) {
-            ca.global_sum = nullptr;
-            if (dist && (e = global_sum(c, fa.np, &ca.global_sum))) return e;
-            ca.dec_partials = fa.partials;
-            ca.dec_np = fa.np;
-            ca.eps = fa.eps;
-            launch_post_tile(ca, 2, c->s);
-            HIPC(hipGetLastError());
-        } else {
-            fa.global_sum = nullptr;
-            if (dist && (e = global_sum(c, fa.np, &fa.global_sum))) return e;
-            if ((e = launch_post_rare(fa, po, c->s))) return e;
-        }
-    }
-    return PGMG_OK;
+    const bool r2 = l == 0 && mode == 0 && fr2_want && !dist && !recomp && c->nb >= 2 &&
+                    !is_dist(c, 1) && tuning_int("PGMG_F_R2", 1) != 0;
+    const int np = tile ? tile_np(c, l, true)
+                        : r2 ? post_r2_blocks(L.N, po.jc0, po.jc1) : fused_blocks(L.N, po.jc0, po.jc1);
+    return enqueue_post_half(c, l, mode, po, tile ? &ca : nullptr, np, r2);
 }
 
 int pgmg::enqueue_fused_level(pgmg_ctx *c, int l, int gamma, bool x0_zero, bool pin, bool fr2_want)
@@ -479,74 +519,209 @@ int pgmg::enqueue_fused_level(pgmg_ctx *c, int l, int gamma, bool x0_zero, bool 
 // iterate S on the rows the following k_pre reads (4 past the strip) from the
 // exchanged halos instead of exchanging S.
 // ---------------------------------------------------------------------------
-StripRows pgmg::strip_rows(const Level &L, const Level &C)
+// The finest level while a call's cross-fused cycles are enqueued.  Building an argument block
+// changes none of it: the step that launches a pass moves pr on and consumes sw_adj / recompute.
+template <class T>
+struct CrossState {
+    Grid gA, gB, gS;   // lv[0].A, lv[0].B and the scratch c->S as the call found them
+    T *A, *B, *S;
+    // speculative call: no rare path can run, so the scratch S is free and the level-0
+    // buffers rotate through B and S; A (the call's input) is never written and a rollback
+    // restarts from it
+    bool lean;
+    T *pr;            // pre-smoothed solution of the current cycle (a taken carry: the solution A)
+    int sw_adj;       // the carried pre-smooth's two sweeps: counted by the next finest pass
+    bool recompute;   // the next finest pass recomputes pr's pre-smooth (k_postpre's recompute form)
+
+    const Grid &grid_of(const T *p) const { return p == A ? gA : p == B ? gB : gS; }
+    // (an external input is followed by B: the first k_pre writes B, then B <-> S (lean) or
+    // B <-> A, both free of the input; a carried input -- A itself -- is followed by B as well)
+    T *next_of(const T *p) const { return lean ? (p == B ? S : B) : (p == B ? A : B); }
+};
+
+// st.pr is final.  Its halo rows (6 for k_postpre, 2 for the last k_post) are read only
+// after the whole coarse hierarchy: the exchange runs on the comm's side stream
+// meanwhile (the coarse correction's halo rows are computed locally, kPostExt)
+template <class T>
+static int enqueue_descend(pgmg_ctx *c, const CrossState<T> &st, int gamma)
 {
-    StripRows r;
-    r.jc0 = L.lo / 2;
-    r.jc1 = (L.hi < L.N ? L.hi : L.N - 1) / 2;
-    r.row_lo = L.u0;
-    r.row_hi = L.u1;
-    r.rc_lo = r.jc0 > 1 ? r.jc0 : 1;
-    r.rc_hi = r.jc1 < C.N - 1 ? r.jc1 : C.N - 1;
-    r.x_lo = L.u0 - 4 > 1 ? L.u0 - 4 : 1;
-    r.x_hi = L.u1 + 4 < L.N - 1 ? L.u1 + 4 : L.N - 1;
-    return r;
+    if (is_dist(c, 0)) PGMG_TRY(c->comm->halo_begin(st.grid_of(st.pr), c->lv[0], 6, c->s));
+    return enqueue_children<T>(c, 0, gamma);
 }
 
+// cycle 1: pre-smooth (+ residual, restriction) of the call's input (A, or the caller's
+// array: pgmg_set_problem_device) into B
 template <class T>
-static PreArgsT<T> make_pre(pgmg_ctx *c, const T *x0, T *x2)
+static int enqueue_first_pre(pgmg_ctx *c, CrossState<T> &st, int np)
 {
-    Level &L = c->lv[0], &C = c->lv[1];
-    const StripRows sr = strip_rows(L, C);
-    PreArgsT<T> pa{};
-    pa.x0 = x0;
-    pa.f = G<T>(L.F);
-    pa.x2 = x2;
-    pa.rc = G<T>(C.F);
-    pa.partials = c->partials;
-    pa.stats = c->stats;
-    pa.hh = (T)L.hh;
-    pa.ih = (T)L.ih;
-    pa.N = L.N;
-    pa.P = L.P;
-    pa.Nc = C.N;
-    pa.Pc = C.P;
-    pa.jc0 = sr.jc0;
-    pa.jc1 = sr.jc1;
-    pa.row_lo = sr.row_lo;
-    pa.row_hi = sr.row_hi;
-    pa.rc_lo = sr.rc_lo;
-    pa.rc_hi = sr.rc_hi;
-    pa.gfx = c->rgfx;
-    pa.gsy = c->rgsy;
-    return pa;
+    const bool dist = is_dist(c, 0);
+    if (dist) PGMG_TRY(c->comm->halo(st.gA, c->lv[0], 4, c->s));
+    PreArgsT<T> pa = pre_args<T>(c, 0);
+    pa.x0 = c->call.x_in != nullptr ? static_cast<const T *>(c->call.x_in) : st.A;
+    pa.x2 = st.B;
+    if (c->call.x_in != nullptr) pa.Px = c->call.ext_P;
+    double *lp = chk_partials(c, np, 0);
+    if (lp) pa.partials = lp;
+    const int ev = timed_begin(c, 1);
+    PGMG_TRY(launch_pre(pa, false, true, c->s));
+    PGMG_TRY(timed_end(c, 1, ev));
+    if (!lp) {
+        FixArgsF fa = fix_args(c, np);
+        if (dist) PGMG_TRY(global_sum(c, np, &fa.global_sum));
+        launch_pre_fixup(fa, pa, false, c->s);
+    }
+    st.pr = st.B;
+    return PGMG_OK;
 }
 
+// a k_postpre block of the finest level; phi, x4 / x2, the partials, sw_adj and recompute are
+// the launching step's
 template <class T>
-static PostArgsT<T> make_post(pgmg_ctx *c, const T *phi, T *x2)
+static PostPreArgsT<T> postpre_args(const pgmg_ctx *c)
 {
-    Level &L = c->lv[0], &C = c->lv[1];
-    const StripRows sr = strip_rows(L, C);
-    PostArgsT<T> po{};
-    po.phi = phi;
-    po.ec = G<T>(C.A);
-    po.f = G<T>(L.F);
-    po.x2 = x2;
-    po.partials = c->partials;
-    po.stats = c->stats;
-    po.hh = (T)L.hh;
-    po.ih = (T)L.ih;
-    po.N = L.N;
-    po.P = L.P;
-    po.Nc = C.N;
-    po.Pc = C.P;
-    po.jc0 = sr.jc0;
-    po.jc1 = sr.jc1;
-    po.row_lo = sr.row_lo;
-    po.row_hi = sr.row_hi;
-    po.gfx = c->rgfx;
-    po.gsy = c->rgsy;
-    return po;
+    const Level &L = c->lv[0], &C = c->lv[1];
+    PostPreArgsT<T> q{};
+    q.ec = G<T>(C.A);
+    q.f = G<T>(L.F);
+    q.rc = G<T>(C.F);
+    q.gfx = c->rgfx;
+    q.gsy = c->rgsy;
+    q.stats = c->stats;
+    postpre_geometry(q, L, C);
+    q.fast = (c->cfg.flags & PGMG_FLAG_FAST) != 0 && !is_dist(c, 0);
+    return q;
+}
+
+// a rare path's fix-up block: runs when *cond is set, recomputes without deciding or counting
+static FixArgsF forced_fix(const pgmg_ctx *c, int np, const unsigned *cond)
+{
+    FixArgsF f = fix_args(c, np);
+    f.cond = cond;
+    f.force = 1;
+    f.stats = nullptr;
+    return f;
+}
+
+// The in-stream step after k_postpre q (calls that decide their checks in-stream): the
+// decision into ppflags (on strips from one allreduce of the three sums), then both rare
+// paths, each conditional on its flag; they leave the pre-smoothed iterate in nx
+template <class T>
+static int enqueue_postpre_rare(pgmg_ctx *c, const CrossState<T> &st, const PostPreArgsT<T> &q, T *nx,
+                                int np, int npp)
+{
+    const bool dist = is_dist(c, 0);
+    const StripRows sr = strip_rows(c->lv[0], c->lv[1]);
+    const double *g3 = nullptr;   // all-rank {post, pre, pre-from-x1} sums
+    if (dist) {
+        launch_sum_partials(q.partials1, npp, c->scalar, c->s);
+        launch_sum_partials(q.partials2, npp, c->scalar + 1, c->s);
+        launch_sum_partials(q.partials3, npp, c->scalar + 2, c->s);
+        PGMG_TRY(c->comm->allreduce_sum(c->scalar, 3, c->s));
+        g3 = c->scalar;
+    }
+    launch_postpre_decide(q.partials1, q.partials2, q.stats, npp, g3, c->cfg.eps, c->ppflags, c->s);
+    // rare path 1 (post check fired): S = x1 of the post-smooth, then a full
+    // pre-smooth from S (conditional k_pre + its own fix-up)
+    PostArgsT<T> po = post_args<T>(c, 0);
+    po.phi = st.pr;
+    po.x2 = st.S;
+    po.row_lo = sr.x_lo;
+    po.row_hi = sr.x_hi;
+    launch_post_fixup(forced_fix(c, np, &c->ppflags[0]), po, c->s);
+    PreArgsT<T> p1 = pre_args<T>(c, 0);
+    p1.x0 = st.S;
+    p1.x2 = nx;
+    p1.cond = &c->ppflags[0];
+    PGMG_TRY(launch_pre(p1, false, false, c->s));
+    FixArgsF f1b = fix_args(c, np);
+    f1b.cond = &c->ppflags[0];
+    f1b.global_sum = dist ? c->scalar + 2 : nullptr;
+    launch_pre_fixup(f1b, p1, false, c->s);
+    // rare path 2 (only the pre check fired): S = x2 of the post-smooth, then the
+    // pre-smooth result is J(S) and rc = R r(J(S))
+    PostArgsT<T> p2 = post_args<T>(c, 0);
+    p2.phi = st.pr;
+    p2.x2 = st.S;
+    if (dist) {   // x2 on the strip and 4 rows past it, from the exchanged halos
+        p2.row_lo = sr.x_lo;
+        p2.row_hi = sr.x_hi;
+        p2.fix_sweeps = 2;
+        launch_post_fixup(forced_fix(c, np, &c->ppflags[1]), p2, c->s);
+    } else {
+        p2.cond = &c->ppflags[1];
+        p2.stats = nullptr;
+        PGMG_TRY(launch_post(p2, false, c->s));
+    }
+    PreArgsT<T> p3 = pre_args<T>(c, 0);
+    p3.x0 = st.S;
+    p3.x2 = nx;
+    launch_pre_fixup(forced_fix(c, np, &c->ppflags[1]), p3, false, c->s);
+    return PGMG_OK;
+}
+
+// the solution's buffer becomes L.A (every level-0 grid mirrors the boundary, so any may
+// play any role); the other two keep their order as L.B and the scratch
+template <class T>
+static void set_roles(pgmg_ctx *c, const CrossState<T> &st, const T *sol)
+{
+    Level &L = c->lv[0];
+    L.A = st.grid_of(sol);
+    L.B = sol == st.A ? st.gB : st.gA;
+    c->S = sol == st.A || sol == st.B ? st.gS : st.gB;
+}
+
+// the carry pass (see "The carry" below): x2 (the result) into a grid that is neither the
+// input A nor pr (pr is A itself when this one pass also takes the carry); its post check is
+// this call's, its pre check the carry's
+template <class T>
+static int enqueue_carry_pass(pgmg_ctx *c, CrossState<T> &st, int nq)
+{
+    T *const out = (st.pr == st.B) ? st.S : st.B;
+    PostPreArgsT<T> q = postpre_args<T>(c);
+    q.phi = st.pr;
+    q.x2 = out;
+    q.sw_adj = st.sw_adj - 2;   // the pre-smooth's sweeps count in the call that uses them
+    q.recompute = st.recompute ? 1 : 0;
+    q.partials1 = chk_partials(c, nq, 0);
+    q.partials2 = chk_log(c, nq, 0, 0);
+    c->call.carry_chk = (int)c->chks.size() - 1;
+    if (q.partials1 == nullptr || q.partials2 == nullptr) return set_err(PGMG_ERR_STATE, "carry pass: check log");
+    const int ev = timed_begin(c, 4);
+    PGMG_TRY(launch_postpre(q, c->s));
+    PGMG_TRY(timed_end(c, 4, ev));
+    st.sw_adj = 0;   // consumed by this pass
+    st.recompute = false;
+    set_roles(c, st, out);
+    c->call.carry_made = true;
+    return PGMG_OK;
+}
+
+// last cycle: post-smooth into the next buffer, which takes L.A's role, or into the caller's
+// array (an external output holds the solution instead; the level-0 grids keep their roles)
+template <class T>
+static int enqueue_closing_post(pgmg_ctx *c, const CrossState<T> &st, int np)
+{
+    const bool dist = is_dist(c, 0);
+    T *const xout = static_cast<T *>(c->call.x_out);
+    T *out = xout != nullptr ? xout : st.next_of(st.pr);
+    if (dist) PGMG_TRY(c->comm->halo_end(c->s));
+    PostArgsT<T> po = post_args<T>(c, 0);
+    po.phi = st.pr;
+    po.x2 = out;
+    if (xout != nullptr) po.Po = c->call.ext_P;
+    po.sw_adj = st.sw_adj;
+    double *lp = chk_partials(c, np, 0);
+    if (lp) po.partials = lp;
+    const int ev = timed_begin(c, 2);
+    PGMG_TRY(launch_post(po, true, c->s));
+    PGMG_TRY(timed_end(c, 2, ev));
+    if (!lp) {
+        FixArgsF fa = fix_args(c, np);
+        if (dist) PGMG_TRY(global_sum(c, np, &fa.global_sum));
+        launch_post_fixup(fa, po, c->s);
+    }
+    if (xout == nullptr) set_roles(c, st, out);
+    return PGMG_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -576,23 +751,10 @@ static PostArgsT<T> make_post(pgmg_ctx *c, const T *phi, T *x2)
 template <class T>
 static int enqueue_cross_cycles(pgmg_ctx *c, int n, int gamma)
 {
-    Level &L = c->lv[0], &C = c->lv[1];
+    Level &L = c->lv[0];
     const bool dist = is_dist(c, 0);
-    const StripRows sr = strip_rows(L, C);
-    Grid gA = L.A, gB = L.B, gS = c->S;
-    T *A = G<T>(gA), *B = G<T>(gB);
-    T *S = G<T>(gS);
-    // speculative call: no rare path can run, so the scratch S is free and the level-0
-    // buffers rotate through B and S; A (the call's input) is never written and a rollback
-    // restarts from it
+    const StripRows sr = strip_rows(L, c->lv[1]);
     const bool lean = c->call.lean;
-    auto grid_of = [&](const T *p) -> const Grid * { return p == A ? &gA : p == B ? &gB : &gS; };
-    // (an external input is followed by B: the first k_pre writes B, then B <-> S (lean) or
-    // B <-> A, both free of the input; a carried input -- A itself -- is followed by B as well)
-    auto next_of = [&](const T *p) -> T * { return lean ? (p == B ? S : B) : (p == B ? A : B); };
-    // the caller's array (pgmg_set_problem_device) as the call's input / output
-    const T *in = c->call.x_in != nullptr ? static_cast<const T *>(c->call.x_in) : A;
-    T *const xout = static_cast<T *>(c->call.x_out);
     const int np = fused_blocks(L.N, sr.jc0, sr.jc1);
     const int npp = postpre_blocks(L.N, sr.jc0, sr.jc1);
     const int npp_rc = postpre_blocks(L.N, sr.jc0, sr.jc1, true);   // the recompute form's
@@ -600,196 +762,47 @@ static int enqueue_cross_cycles(pgmg_ctx *c, int n, int gamma)
     // pre-smooth and lv[1].F, its first finest pass the recompute form -- a k_postpre, so a
     // call of one cycle takes it only when it also makes the next); both only on speculative
     // calls on the context's own grids, one GPU
-    const bool make = c->call.carry_make && lean && !dist && xout == nullptr && !c->call.defer_post;
+    const bool make = c->call.carry_make && lean && !dist && c->call.x_out == nullptr && !c->call.defer_post;
     const bool take = c->call.carry_use && lean && !dist && c->call.x_in == nullptr && (n > 1 || make);
+    CrossState<T> st{L.A, L.B, c->S, G<T>(L.A), G<T>(L.B), G<T>(c->S), lean, nullptr, take ? 2 : 0, take};
     if (tuning_int("PGMG_ROLE_TRACE", 0))   // measurement build: which grids play which role
-        fprintf(stderr, "roles A %p B %p S %p n %d take %d make %d\n", gA.base, gB.base, gS.base, n,
+        fprintf(stderr, "roles A %p B %p S %p n %d take %d make %d\n", st.gA.base, st.gB.base, st.gS.base, n,
                 (int)take, (int)make);
     c->call.carry_use = false;
     c->call.carry_made = false;
     c->call.carry_took = take;
-    int sw_adj = take ? 2 : 0;   // the carried pre-smooth's two sweeps: counted by the next pass
-    FixArgsF fa{};
-    fa.partials = c->partials;
-    fa.np = np;
-    fa.eps = c->cfg.eps;
-    fa.stats = c->stats;
-    int e, ev;
-    T *pr;   // pre-smoothed solution of the current cycle (a taken carry: the solution A)
-    bool recompute = take;   // the next finest pass recomputes pr's pre-smooth
-    if (take) {
-        pr = A;
-    } else {
-        // cycle 1: pre-smooth (+ residual, restriction) A -> B
-        if (dist && (e = c->comm->halo(gA, L, 4, c->s))) return e;
-        PreArgsT<T> pa = make_pre<T>(c, in, B);
-        if (c->call.x_in != nullptr) pa.Px = c->call.ext_P;
-        double *lp = chk_partials(c, np, 0);
-        if (lp) pa.partials = lp;
-        ev = timed_begin(c, 1);
-        if ((e = launch_pre(pa, false, true, c->s))) return e;
-        if ((e = timed_end(c, 1, ev))) return e;
-        if (!lp) {
-            if (dist && (e = global_sum(c, np, &fa.global_sum))) return e;
-            launch_pre_fixup(fa, pa, false, c->s);
-            fa.global_sum = nullptr;
-        }
-        pr = B;
-    }
-    // its halo rows (6 for k_postpre, 2 for the last k_post) are final now and read only
-    // after the whole coarse hierarchy: the exchange runs on the comm's side stream
-    // meanwhile (the coarse correction's halo rows are computed locally, kPostExt)
-    if (dist && (e = c->comm->halo_begin(*grid_of(pr), L, 6, c->s))) return e;
-    if ((e = enqueue_children<T>(c, 0, gamma))) return e;
-    auto postpre_args = [&](T *phi, T *x4) {
-        PostPreArgsT<T> q{};
-        q.phi = phi;
-        q.ec = G<T>(C.A);
-        q.f = G<T>(L.F);
-        q.x4 = x4;
-        q.rc = G<T>(C.F);
-        q.gfx = c->rgfx;
-        q.gsy = c->rgsy;
-        q.stats = c->stats;
-        postpre_geometry(q, L, C);
-        q.fast = (c->cfg.flags & PGMG_FLAG_FAST) != 0 && !dist;
-        q.sw_adj = sw_adj;
-        sw_adj = 0;
-        q.recompute = recompute ? 1 : 0;
-        recompute = false;
-        return q;
-    };
+    if (take) st.pr = st.A;
+    else PGMG_TRY(enqueue_first_pre(c, st, np));
+    PGMG_TRY(enqueue_descend(c, st, gamma));
     for (int k = 1; k < n; ++k) {
-        T *nx = next_of(pr);
-        if (dist && (e = c->comm->halo_end(c->s))) return e;
-        const int nq = recompute ? npp_rc : npp;
-        PostPreArgsT<T> q = postpre_args(pr, nx);
+        T *nx = st.next_of(st.pr);
+        if (dist) PGMG_TRY(c->comm->halo_end(c->s));
+        const int nq = st.recompute ? npp_rc : npp;
+        PostPreArgsT<T> q = postpre_args<T>(c);
+        q.phi = st.pr;
+        q.x4 = nx;
+        q.sw_adj = st.sw_adj;
+        q.recompute = st.recompute ? 1 : 0;
         q.partials1 = lean ? chk_partials(c, nq, 0) : c->partials;
         q.partials2 = lean ? chk_partials(c, nq, 0) : c->partials2;
         q.partials3 = (dist && !lean) ? c->partials3 : nullptr;   // lean: no rare path runs
         const int slot = q.recompute ? 5 : 3;   // (the recompute form: its own timed slot)
-        ev = timed_begin(c, slot);
-        if ((e = launch_postpre(q, c->s))) return e;
-        if ((e = timed_end(c, slot, ev))) return e;
-        const double *g3 = nullptr;   // all-rank {post, pre, pre-from-x1} sums
-        if (lean) {
-            pr = nx;
-            if (dist && (e = c->comm->halo_begin(*grid_of(pr), L, 6, c->s))) return e;
-            if ((e = enqueue_children<T>(c, 0, gamma))) return e;
-            continue;
-        }
-        if (dist) {
-            launch_sum_partials(q.partials1, npp, c->scalar, c->s);
-            launch_sum_partials(q.partials2, npp, c->scalar + 1, c->s);
-            launch_sum_partials(q.partials3, npp, c->scalar + 2, c->s);
-            if ((e = c->comm->allreduce_sum(c->scalar, 3, c->s))) return e;
-            g3 = c->scalar;
-        }
-        launch_postpre_decide(q.partials1, q.partials2, q.stats, npp, g3, c->cfg.eps, c->ppflags,
-                              c->s);
-        // rare path 1 (post check fired): S = x1 of the post-smooth, then a full
-        // pre-smooth from S (conditional k_pre + its own fix-up)
-        PostArgsT<T> po = make_post<T>(c, pr, S);
-        po.row_lo = sr.x_lo;
-        po.row_hi = sr.x_hi;
-        FixArgsF f1 = fa;
-        f1.cond = &c->ppflags[0];
-        f1.force = 1;
-        f1.stats = nullptr;
-        launch_post_fixup(f1, po, c->s);
-        PreArgsT<T> p1 = make_pre<T>(c, S, nx);
-        p1.cond = &c->ppflags[0];
-        if ((e = launch_pre(p1, false, false, c->s))) return e;
-        FixArgsF f1b = fa;
-        f1b.cond = &c->ppflags[0];
-        f1b.global_sum = dist ? c->scalar + 2 : nullptr;
-        launch_pre_fixup(f1b, p1, false, c->s);
-        // rare path 2 (only the pre check fired): S = x2 of the post-smooth, then the
-        // pre-smooth result is J(S) and rc = R r(J(S))
-        PostArgsT<T> p2 = make_post<T>(c, pr, S);
-        if (dist) {   // x2 on the strip and 4 rows past it, from the exchanged halos
-            p2.row_lo = sr.x_lo;
-            p2.row_hi = sr.x_hi;
-            p2.fix_sweeps = 2;
-            FixArgsF f2a = fa;
-            f2a.cond = &c->ppflags[1];
-            f2a.force = 1;
-            f2a.stats = nullptr;
-            launch_post_fixup(f2a, p2, c->s);
-        } else {
-            p2.cond = &c->ppflags[1];
-            p2.stats = nullptr;
-            if ((e = launch_post(p2, false, c->s))) return e;
-        }
-        PreArgsT<T> p3 = make_pre<T>(c, S, nx);
-        FixArgsF f2 = fa;
-        f2.cond = &c->ppflags[1];
-        f2.force = 1;
-        f2.stats = nullptr;
-        launch_pre_fixup(f2, p3, false, c->s);
-        pr = nx;   // final after the rare paths
-        if (dist && (e = c->comm->halo_begin(*grid_of(pr), L, 6, c->s))) return e;
-        if ((e = enqueue_children<T>(c, 0, gamma))) return e;
+        const int ev = timed_begin(c, slot);
+        PGMG_TRY(launch_postpre(q, c->s));
+        PGMG_TRY(timed_end(c, slot, ev));
+        st.sw_adj = 0;   // consumed by this pass
+        st.recompute = false;
+        if (!lean) PGMG_TRY(enqueue_postpre_rare(c, st, q, nx, np, npp));
+        st.pr = nx;   // final (after the rare paths)
+        PGMG_TRY(enqueue_descend(c, st, gamma));
     }
-    // last cycle: post-smooth
-    if (c->call.defer_post) {   // enqueued by run_cycles_spec after the validation
-        c->call.pend_pr = pr;
+    if (c->call.defer_post) {   // the last k_post: enqueued by run_cycles_spec after the validation
+        c->call.pend_pr = st.pr;
         return PGMG_OK;
     }
-    // the solution's buffer becomes L.A (every level-0 grid mirrors the boundary, so any may
-    // play any role); an external output holds the solution instead (the level-0 grids keep
-    // their roles)
-    auto set_roles = [&](const T *sol) {
-        const Grid *all[3] = {&gA, &gB, &gS};
-        std::vector<Grid> rest;
-        for (const Grid *g : all)
-            if (g != grid_of(sol)) rest.push_back(*g);
-        L.A = *grid_of(sol);
-        L.B = rest[0];
-        c->S = rest[1];
-    };
-    if (make) {
-        // the carry pass: x2 (the result) into a grid that is neither the input A nor pr (pr is
-        // A itself when this one pass also takes the carry); its post check is this call's, its
-        // pre check the carry's
-        T *const out = (pr == B) ? S : B;
-        const int nq = recompute ? npp_rc : npp;
-        PostPreArgsT<T> q = postpre_args(pr, nullptr);
-        q.x2 = out;
-        q.sw_adj -= 2;   // the pre-smooth's sweeps count in the call that uses them
-        q.partials1 = chk_partials(c, nq, 0);
-        q.partials2 = chk_log(c, nq, 0, 0);
-        c->call.carry_chk = (int)c->chks.size() - 1;
-        if (q.partials1 == nullptr || q.partials2 == nullptr) return set_err(PGMG_ERR_STATE, "carry pass: check log");
-        ev = timed_begin(c, 4);
-        if ((e = launch_postpre(q, c->s))) return e;
-        if ((e = timed_end(c, 4, ev))) return e;
-        set_roles(out);
-        c->call.carry_made = true;
-        return PGMG_OK;
-    }
-    if (recompute) return set_err(PGMG_ERR_STATE, "a taken carry without a k_postpre");
-    T *out = xout != nullptr ? xout : next_of(pr);
-    if (dist && (e = c->comm->halo_end(c->s))) return e;
-    PostArgsT<T> po = make_post<T>(c, pr, out);
-    if (xout != nullptr) po.Po = c->call.ext_P;
-    po.sw_adj = sw_adj;
-    double *lp = chk_partials(c, np, 0);
-    if (lp) po.partials = lp;
-    ev = timed_begin(c, 2);
-    if ((e = launch_post(po, true, c->s))) return e;
-    if ((e = timed_end(c, 2, ev))) return e;
-    if (!lp) {
-        if (dist && (e = global_sum(c, np, &fa.global_sum))) return e;
-        launch_post_fixup(fa, po, c->s);
-    }
-    if (xout != nullptr) {
-    } else if (lean) {
-        set_roles(out);
-    } else if (out != A) {
-        std::swap(L.A, L.B);
-    }
-    return PGMG_OK;
+    if (make) return enqueue_carry_pass(c, st, st.recompute ? npp_rc : npp);
+    if (st.recompute) return set_err(PGMG_ERR_STATE, "a taken carry without a k_postpre");
+    return enqueue_closing_post(c, st, np);
 }
 
 // MultigridSolver::v_cycle / w_cycle (MultiGrid.hpp:57-136) on level l
@@ -801,11 +814,9 @@ static int enqueue_cycle_t(pgmg_ctx *c, int l, int gamma, bool x0_zero)
     Level &L = c->lv[l];
     Level &C = c->lv[l + 1];
     const bool dist = is_dist(c, l);
-    int e;
-    if (dist && l > 0 && (e = c->comm->halo(L.F, L, 1, c->s))) return e;
-    e = enqueue_smooth_t<T>(c, l, 0, c->cfg.v1, x0_zero);
-    if (e) return e;
-    if (dist && (e = c->comm->halo(L.A, L, 2, c->s))) return e;
+    if (dist && l > 0) PGMG_TRY(c->comm->halo(L.F, L, 1, c->s));
+    PGMG_TRY(enqueue_smooth_t<T>(c, l, 0, c->cfg.v1, x0_zero));
+    if (dist) PGMG_TRY(c->comm->halo(L.A, L, 2, c->s));
     ResRestrictArgsT<T> r{};
     r.x = G<T>(L.A);
     r.f = G<T>(L.F);
@@ -819,8 +830,8 @@ static int enqueue_cycle_t(pgmg_ctx *c, int l, int gamma, bool x0_zero)
     r.jc0 = L.lo / 2 > 1 ? L.lo / 2 : 1;
     r.jc1 = (L.hi + 1) / 2 < C.N - 1 ? (L.hi + 1) / 2 : C.N - 1;
     launch_res_restrict(r, c->s);
-    if ((e = enqueue_children<T>(c, l, gamma))) return e;
-    if (dist && is_dist(c, l + 1) && (e = c->comm->halo(C.A, C, 2, c->s))) return e;
+    PGMG_TRY(enqueue_children<T>(c, l, gamma));
+    if (dist && is_dist(c, l + 1)) PGMG_TRY(c->comm->halo(C.A, C, 2, c->s));
     ProlongArgsT<T> p{};
     p.c = G<T>(C.A);
     p.fine = G<T>(L.A);
@@ -846,19 +857,14 @@ int pgmg::enqueue_cycle(pgmg_ctx *c, int l, int gamma, bool x0_zero)
 template <class T>
 static int enqueue_last_post_t(pgmg_ctx *c)
 {
-    Level &L = c->lv[0];
-    const StripRows sr = strip_rows(L, c->lv[1]);
-    PostArgsT<T> po = make_post<T>(c, static_cast<const T *>(c->call.pend_pr), static_cast<T *>(c->call.x_out));
+    PostArgsT<T> po = post_args<T>(c, 0);
+    po.phi = static_cast<const T *>(c->call.pend_pr);
+    po.x2 = static_cast<T *>(c->call.x_out);
     po.Po = c->call.ext_P;
     const int ev = timed_begin(c, 2);
     PGMG_TRY(launch_post(po, true, c->s));
     PGMG_TRY(timed_end(c, 2, ev));
-    FixArgsF fa{};
-    fa.partials = c->partials;
-    fa.np = fused_blocks(L.N, sr.jc0, sr.jc1);
-    fa.eps = c->cfg.eps;
-    fa.stats = c->stats;
-    launch_post_fixup(fa, po, c->s);
+    launch_post_fixup(fix_args(c, fused_blocks(po.N, po.jc0, po.jc1)), po, c->s);
     HIPC(hipGetLastError());
     HIPC(hipEventRecord(c->ev1, c->s));
     c->call.pend_pr = nullptr;
@@ -879,37 +885,30 @@ int pgmg::run_cycles_plain(pgmg_ctx *c, int ncycles, int gamma, bool rec0)
                            !c->cross;
     if (use_graph && !c->gexec) {
         // first cycle eagerly (sets kernel attributes), the rest from a captured graph
-        int e = enqueue_cycle(c, 0, 1, false);
-        if (e) return e;
+        PGMG_TRY(enqueue_cycle(c, 0, 1, false));
         HIPC(hipGetLastError());
         --ncycles;
         hipGraph_t g = nullptr;
         HIPC(hipStreamBeginCapture(c->s, hipStreamCaptureModeThreadLocal));
-        e = enqueue_cycle(c, 0, 1, false);
+        const int rc = enqueue_cycle(c, 0, 1, false);   // (the capture ends on every path)
         hipError_t ce = hipStreamEndCapture(c->s, &g);
-        if (e) return e;
+        if (rc) return rc;
         if (ce != hipSuccess) return set_err(PGMG_ERR_HIP, std::string("capture: ") + hipGetErrorString(ce));
         HIPC(hipGraphInstantiate(&c->gexec, g, nullptr, nullptr, 0));
         HIPC(hipGraphDestroy(g));
     }
     if (c->cross && !use_graph) {
-        int e = c->fp32 ? enqueue_cross_cycles<float>(c, ncycles, gamma)
-                        : enqueue_cross_cycles<double>(c, ncycles, gamma);
-        if (e) return e;
+        PGMG_TRY(c->fp32 ? enqueue_cross_cycles<float>(c, ncycles, gamma)
+                         : enqueue_cross_cycles<double>(c, ncycles, gamma));
         HIPC(hipGetLastError());
         HIPC(hipEventRecord(c->ev1, c->s));
         return PGMG_OK;
     }
     for (int k = 0; k < ncycles; ++k) {
-        if (use_graph) {
-            HIPC(hipGraphLaunch(c->gexec, c->s));
-        } else {
-            int e = enqueue_cycle(c, 0, gamma, false);
-            if (e) return e;
-        }
+        if (use_graph) HIPC(hipGraphLaunch(c->gexec, c->s));
+        else PGMG_TRY(enqueue_cycle(c, 0, gamma, false));
     }
     HIPC(hipGetLastError());
     HIPC(hipEventRecord(c->ev1, c->s));
     return PGMG_OK;
 }
-

@@ -77,7 +77,7 @@ struct PostArgsT {
     long long Pr2;
     int Nr2;
     // added to the sweeps the pass counts (stats[0] += 2 + sw_adj): +2 on the first finest pass
-    // of a call that took over a carried pre-smooth (pgmg_ctx.hip "carry"), whose two sweeps
+    // of a call that took over a carried pre-smooth (pgmg_cycle.hip "carry"), whose two sweeps
     // were run by the previous call's last pass
     int sw_adj;
 };
@@ -106,7 +106,7 @@ struct PostPreArgsT {
     int rows_per_block;
     int fast;                   // PGMG_FLAG_FAST (one GPU, f regenerated or stored)
     // non-null: the carry pass, the LAST finest pass of a call that also runs the next call's
-    // pre-smooth (pgmg_ctx.hip "carry"): x2, the call's result, is stored here instead of x4
+    // pre-smooth (pgmg_cycle.hip "carry"): x2, the call's result, is stored here instead of x4
     // (x4 = nullptr); its restricted residual goes to rc as usual
     T *x2;
     int sw_adj;                 // stats[0] += 4 + sw_adj (the carry pass: -2; see PostArgsT)

@@ -1,5 +1,5 @@
 // pgmg_host.h — shared by the orchestration's files (mapped in pgmg_ctx.hip's header): error
-// macros, the functions that cross a file boundary, two argument-block builders.  Host only.
+// macros, the functions that cross a file boundary, the argument-block builders they share.  Host only.
 #pragma once
 #include "pgmg_ctx.h"
 #include "pgmg_fused.h"
@@ -108,21 +108,30 @@ inline TailArgsT<T> tail_args(const pgmg_ctx *c)
     return t;
 }
 
-// level geometry of a k_postpre-shaped pass (k_postpre, fused smooth(3)) on level L above C
+// level geometry of a fused pass's argument block on level L above C (its strip's rows)
+template <class Args>
+inline StripRows pass_geometry(Args &a, const Level &L, const Level &C)
+{
+    using T = decltype(a.hh);
+    const StripRows sr = strip_rows(L, C);
+    a.hh = (T)L.hh;
+    a.ih = (T)L.ih;
+    a.N = L.N;
+    a.P = L.P;
+    a.Nc = C.N;
+    a.Pc = C.P;
+    a.jc0 = sr.jc0;
+    a.jc1 = sr.jc1;
+    a.row_lo = sr.row_lo;
+    a.row_hi = sr.row_hi;
+    return sr;
+}
+
+// ... of a k_postpre-shaped pass (k_postpre, fused smooth(3))
 template <class T>
 inline void postpre_geometry(PostPreArgsT<T> &q, const Level &L, const Level &C)
 {
-    const StripRows sr = strip_rows(L, C);
-    q.hh = (T)L.hh;
-    q.ih = (T)L.ih;
-    q.N = L.N;
-    q.P = L.P;
-    q.Nc = C.N;
-    q.Pc = C.P;
-    q.jc0 = sr.jc0;
-    q.jc1 = sr.jc1;
-    q.row_lo = sr.row_lo;
-    q.row_hi = sr.row_hi;
+    const StripRows sr = pass_geometry(q, L, C);
     q.rc_lo = sr.rc_lo;
     q.rc_hi = sr.rc_hi;
 }

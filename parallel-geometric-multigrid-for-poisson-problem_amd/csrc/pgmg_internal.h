@@ -71,7 +71,7 @@ inline double norm2_threshold(double eps)
 }
 
 // one early-exit check recorded by a speculative call: the producing pass's per-block
-// partial sums of r^2 (see pgmg_ctx.hip, "speculative calls")
+// partial sums of r^2 (see pgmg_spec.hip, "speculative calls")
 struct CheckRef {
     const double *partials;
     long long np;

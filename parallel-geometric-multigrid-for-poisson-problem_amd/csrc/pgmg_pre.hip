@@ -260,7 +260,7 @@ __global__ __launch_bounds__(256) void k_pre(PreArgsT<T> a)
 }
 
 // A coarse level's pre-smooth whose check is predicted to fire (speculative calls, levels that
-// converged: pgmg_ctx.hip "predicted to fire"): x1 = J(x0) (J(0) on a level entered with
+// converged: pgmg_spec.hip "predicted to fire"): x1 = J(x0) (J(0) on a level entered with
 // x0 = 0) is the result, rc = R r(x1), one sweep and one exit booked, the "pre fired" flag the
 // level's RECOMP k_post reads set -- what k_pre + k_pre_rare compute when the check fires, in
 // one launch; the partials confirm it afterwards
