@@ -39,6 +39,28 @@
  *     pgmg_norm      DynamicGridUtils::norm        DynamicGridUtils.hpp:21-27
  *     pgmg_rhs       DynamicGridUtils::compute_rhs DynamicGridUtils.hpp:111-124
  *
+ * Special values.  The bit-for-bit promise holds for any input words, not only for ordinary
+ * numbers: every output word that the reference (mg_cpu_exec) leaves non-NaN is bitwise the
+ * reference's -- the sign of a zero, subnormals (nothing is flushed, in fp64 or fp32) and
+ * +-Inf included -- and an output word is NaN exactly where the reference's is.  A NaN's sign
+ * and payload are unspecified (x86 and CDNA produce different default NaNs, and a compiler may
+ * commute the operands of an add), so pgmg_solution_hash of a grid that holds a NaN is not
+ * comparable between the two.  Early-exit decisions, and with them the sweep and exit counts
+ * of pgmg_stats, are the reference's for any norm: sqrt(sum r^2) < eps does not fire on a sum
+ * that is NaN or that overflowed to Inf, and fires on a sum of exactly 0 unless eps is 0.
+ * fp32 contexts follow the same rule against the fp32 restatement of the reference, and
+ * convert the caller's doubles at the ABI by IEEE round-to-nearest-even (overflow to Inf,
+ * gradual underflow, NaN stays NaN).  One deliberate exception to "converted at the ABI":
+ * pgmg_set_problem_device only binds.  The solution of a device-bound problem is the caller's
+ * array, so until the first call writes it pgmg_get_solution returns the caller's own doubles,
+ * unrounded, also in an fp32 context; the first call reads them rounded as above and leaves the
+ * fp32 result, frame included, in the array (tests/test_gpu_special_cycles.py::
+ * test_abi_f32_conversion[device]).  Two things the reference's F-cycle does, kept as they are:
+ * it reads no frame word of phi, and a -0 of phi leaves no trace in its result (test_f_cycles).
+ * Pinned by tests/test_oracle_special.py (the restatement
+ * against the compiled reference) and tests/test_gpu_special_ops.py, test_gpu_special_cycles.py
+ * (the library against the restatement).
+ *
  * Threading: a context is driven by one host thread; not thread-safe.
  */
 #ifndef PGMG_H

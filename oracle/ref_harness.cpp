@@ -22,6 +22,8 @@
 //   cycle <k> relerr <e> res <r> center <phi[(N/2)*N+N/2]> hash <fnv64> sweeps <s> exits <x>
 //   seconds <wall time of the reference's cycle call alone>  (bench.py's cpu_baseline)
 // and, if given, writes phi after the last cycle as raw little-endian doubles.
+// Two more modes take their arrays from files: O (the op-level entries, op_mode) and P (V- or
+// W-cycles on a caller's phi0 and f, problem_mode); their usage stands above each.
 //
 // operator new[] is calloc-backed: the reference reads the never-written
 // boundary of `new double[L]` residual buffers (Smoother.hpp:75-76), which is
@@ -138,9 +140,47 @@ static int op_mode(int argc, char **argv)
     return 0;
 }
 
+// Custom-problem mode: ref_harness P <V|W> <N> <cycles> <eps> <alpha> <n_coarse> <h> <in.bin> <out.bin>
+// in.bin : phi0[N*N], f[N*N]  (doubles; any words: signed zeros, subnormals, Inf, NaN)
+// out.bin: phi[N*N] after every cycle, `cycles` grids
+// n_coarse 0: the reference's default; h "-": 1 / (N - 1)
+// Prints one line per cycle: cycle <k> sweeps <s> exits <x>  (cumulative, as the cycle modes)
+static int problem_mode(int argc, char **argv)
+{
+    if (argc < 11) return 2;
+    const char kind = argv[2][0];
+    const int N = std::atoi(argv[3]);
+    const int cycles = std::atoi(argv[4]);
+    const double eps = std::atof(argv[5]);
+    const int alpha = std::atoi(argv[6]);
+    const int n_coarse = std::atoi(argv[7]);
+    const double h = std::strcmp(argv[8], "-") != 0 ? std::atof(argv[8]) : 1.0 / (N - 1);
+    if ((kind != 'V' && kind != 'W') || N < 3 || cycles < 1 || alpha < 1) return 2;
+    const long long L = (long long)N * N;
+    std::vector<double> in(2 * L);
+    FILE *fp = std::fopen(argv[9], "rb");
+    if (!fp || std::fread(in.data(), 8, in.size(), fp) != in.size()) return 3;
+    std::fclose(fp);
+    double *phi = in.data(), *f = in.data() + L;
+    CountingJacobi sm(eps);
+    MultigridSolver mg(&sm, alpha, N);
+    if (n_coarse > 0) mg.N_coarse = n_coarse;
+    fp = std::fopen(argv[10], "wb");
+    if (!fp) return 3;
+    for (int k = 1; k <= cycles; ++k) {
+        if (kind == 'V') mg.v_cycle(phi, f, N, h);
+        else mg.w_cycle(phi, f, N, h);
+        std::fwrite(phi, 8, (size_t)L, fp);
+        std::printf("cycle %d sweeps %lld exits %lld\n", k, sm.sweeps, sm.exits);
+    }
+    std::fclose(fp);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     if (argc > 1 && argv[1][0] == 'O') return op_mode(argc, argv);
+    if (argc > 1 && argv[1][0] == 'P') return problem_mode(argc, argv);
     if (argc < 5) {
         std::fprintf(stderr, "usage: %s <V|W|F|G> <N> <cycles> <eps> [phi_out.bin|- [alpha [n_coarse "
                              "[a p q [h]]]]]\n", argv[0]);

@@ -313,9 +313,14 @@ static int spec_plan_segment(pgmg_ctx *c, int seg)
             if (c->hist.lvl_hist[l].size() < 2 && !c->hist.lvl_exact[l]) return 3;
     if (c->comm != nullptr) return seg;   // (strips: every rank must agree)
     const double lim = c->cfg.eps * 100.0, flim = c->cfg.eps * 0.25;
-    // cycles until last * rho^k falls below t
+    // cycles until last * rho^k falls below t; kNever where it never does: a norm of Inf (r^2
+    // overflowed), t = 0 (eps = 0) or a decay that is NaN (Inf / Inf) give a quotient of Inf
+    // or NaN, which must not reach the cast (undefined for a value no int holds)
+    constexpr int kNever = 1 << 20;
     auto cycles_to = [](double last, double rho, double t) {
-        return last > t ? (int)std::floor(std::log(t / last) / std::log(rho)) : 0;
+        if (!(last > t)) return 0;
+        const double k = std::floor(std::log(t / last) / std::log(rho));
+        return k < (double)kNever ? (int)std::max(k, 0.0) : kNever;
     };
     // candidate split points: a level's last cycle before it can be predicted to fire (its
     // norm under eps / 4 for two visits)

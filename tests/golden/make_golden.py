@@ -3,7 +3,7 @@
 
 Run in the build container only (needs /root/reference and `make -C oracle ref`):
 
-    python tests/golden/make_golden.py [--big] [--params-only] [--problem-only]
+    python tests/golden/make_golden.py [--big] [--params-only] [--problem-only] [--special-only]
 
 The reference (2_part_MG/MultiGrid.hpp + Smoother.hpp + DynamicGridUtils.hpp) is compiled
 unmodified by oracle/Makefile into oracle/_ref/ref_harness; this script only runs it and
@@ -27,6 +27,16 @@ stores inputs/outputs as data:
                      a / (N - 1)).  A relerr that is not finite (p = 0: the exact solution is
                      0 everywhere) is stored as null.  Recorded results of the reference's own
                      unmodified code, as above.  (--problem-only regenerates this file alone)
+  special_ops.npz    inputs made of IEEE special values (signed zeros, subnormals, +-1e308, NaN
+                     and Inf seeds; SPECIAL_OP_INPUTS) and the reference's residual, restriction,
+                     prolongation and smoother outputs on them, N = 17 and 33
+  special_cycles.npz the reference's V- and W-cycles on the input families of
+                     tests/special_values.py (SPECIAL_CASES): per cycle the cumulative sweep and
+                     exit counts, the census of phi (-0, subnormal, Inf, NaN words) and its
+                     canonical-NaN hash (special_values.canon_hash); the last cycle's full phi for
+                     N = 17 and, V-cycles, N = 33.
+                     Recorded inputs and outputs of the reference's own unmodified code
+                     (ref_harness modes O and P).  (--special-only regenerates these two alone)
   phi_<K><N>_c<k>.npy  full phi vectors for small N (N <= 129)
   ops_N<N>.npz       seeded random inputs and the reference's residual, restriction,
                      prolongation and smoother outputs (op-level known-answer tests)
@@ -285,6 +295,86 @@ def make_ops(N, seed, tmp):
              smooth10=parts[4].reshape(N, N))
 
 
+# Special values: the cases are special_values.reference_cases(), 2 cycles each.
+SPECIAL_CYCLES = 2
+
+
+def special_op_inputs(N, which):
+    """x, f (N x N) and e (Nc x Nc) of one of the three special op inputs."""
+    rng = np.random.default_rng(9000 + N + 100 * ("sparse", "big", "seed").index(which))
+    Nc = (N - 1) // 2 + 1
+
+    def one(n):
+        if which == "sparse":   # +-0, a few point sources and subnormals
+            a = np.where(rng.random((n, n)) < 0.5, 0.0, -0.0)
+            k = rng.random((n, n))
+            a = np.where(k < 0.04, rng.choice([1.0, -2.5, 0.375], (n, n)), a)
+            a = np.where((k >= 0.04) & (k < 0.12),
+                         rng.choice([5e-324, -5e-324, 3e-310, -1.5e-308, 2.2e-308], (n, n)), a)
+            return a
+        if which == "big":      # sums of four overflow, differences cancel
+            return rng.uniform(-1.0, 1.0, (n, n)) * 1e308
+        a = rng.uniform(-1.0, 1.0, (n, n))
+        return a
+    x, f, e = one(N), one(N), one(Nc)
+    if which == "seed":
+        x[N // 3, 2 * N // 3] = np.nan
+        x[N - 2, 1] = -np.inf
+        f[2 * N // 3, N // 3] = np.inf
+        e[Nc // 2, Nc // 2] = np.nan
+        e[1, Nc - 2] = np.inf
+    return x, f, e
+
+
+def write_special():
+    import sys
+    sys.path.insert(0, str(REPO / "tests"))
+    sys.path.insert(0, str(REPO / "oracle"))
+    import special_values as sv
+    ops, cyc = {}, {}
+    with tempfile.TemporaryDirectory() as tmp:
+        pin, pout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
+        for N in (17, 33):
+            Nc, h, eps = (N - 1) // 2 + 1, 1.0 / (N - 1), 1e-7
+            for which in ("sparse", "big", "seed"):
+                x, f, e = special_op_inputs(N, which)
+                np.concatenate([x.ravel(), f.ravel(), e.ravel()]).astype("<f8").tofile(pin)
+                subprocess.run([str(HARNESS), "O", str(N), repr(h), repr(eps), pin, pout],
+                               check=True)
+                o = np.fromfile(pout, dtype="<f8")
+                L, Lc = N * N, Nc * Nc
+                parts = np.split(o, np.cumsum([L, Lc, L, L]))
+                t = f"N{N}_{which}_"
+                ops.update({t + "x": x, t + "f": f, t + "e": e,
+                            t + "residual": parts[0].reshape(N, N),
+                            t + "restrict": parts[1].reshape(Nc, Nc),
+                            t + "prolong": parts[2].reshape(N, N),
+                            t + "smooth1": parts[3].reshape(N, N),
+                            t + "smooth10": parts[4].reshape(N, N)})
+        for kind, N, fam, nc, alpha, eps in sv.reference_cases():
+            phi0, f = sv.family(fam, N)
+            f = sv.analytic_f(N) if f is None else f
+            np.concatenate([phi0.ravel(), f.ravel()]).astype("<f8").tofile(pin)
+            out = subprocess.run([str(HARNESS), "P", kind, str(N), str(SPECIAL_CYCLES), repr(eps),
+                                  str(alpha), str(nc), "-", pin, pout],
+                                 check=True, capture_output=True, text=True).stdout
+            rows = [l.split() for l in out.splitlines() if l.startswith("cycle")]
+            assert len(rows) == SPECIAL_CYCLES, (kind, N, fam, out)
+            phi = np.fromfile(pout, dtype="<f8").reshape(SPECIAL_CYCLES, N, N)
+            t = f"{kind}_{N}_{fam}_nc{nc}_a{alpha}_eps{eps:g}_"
+            cyc[t + "sweeps"] = np.array([int(r[3]) for r in rows], dtype=np.int64)
+            cyc[t + "exits"] = np.array([int(r[5]) for r in rows], dtype=np.int64)
+            cyc[t + "census"] = np.array([[sv.census(p)[k] for k in ("nz", "sub", "inf", "nan")]
+                                          for p in phi], dtype=np.int64)
+            cyc[t + "hash"] = np.array([int(sv.canon_hash(p), 16) for p in phi], dtype=np.uint64)
+            if N == 17 or (N == 33 and kind == "V"):    # full arrays: the last cycle's phi
+                cyc[t + "phi"] = phi[-1]
+    np.savez_compressed(HERE / "special_ops.npz", **ops)
+    np.savez_compressed(HERE / "special_cycles.npz", **cyc)
+    print(f"wrote {len(ops) // 8} op cases and {len(sv.reference_cases())} cycle cases to "
+          "special_*.npz")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--big", action="store_true", help="also run the full-size BIG cases")
@@ -295,9 +385,14 @@ def main():
                     help="write cycles_params.json only (PARAM_CASES)")
     ap.add_argument("--problem-only", action="store_true",
                     help="write cycles_problem.json only (PROBLEM_CASES)")
+    ap.add_argument("--special-only", action="store_true",
+                    help="write special_ops.npz and special_cycles.npz only")
     args = ap.parse_args()
     if not HARNESS.exists():
         raise SystemExit("build the reference harness first: make -C oracle ref")
+    if args.special_only:
+        write_special()
+        return
     if not args.params_only:
         write_problem()
     if args.problem_only:
