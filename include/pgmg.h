@@ -543,6 +543,73 @@ int pgmg_fmg_bc(pgmg_ctx *ctx, int nu, double omega);
  * N >= 9, world 1.  Leaves phi changed (call set_problem again before parity checks). */
 int pgmg_fmg_interp_time(pgmg_ctx *ctx, int reps, double *ms_per_pass, double *bytes);
 
+/* ---- Fourth-order solves by Richardson extrapolation -------------------------------------
+ * The 5-point discretisation is second order: for smooth data its solution is
+ * u_h = u + h^2 c(x) + O(h^4).  pgmg_solve_extrap(ctx, opts, nu, omega, info) solves the same
+ * continuous problem on the grid and on the grid of every second point and combines the two: at
+ * the coincident points u_h + (u_h - u_2h) / 3 is O(h^4), and the correction (u_h - u_2h) / 3 is
+ * a smooth field of size h^2 whose cubic interpolation to the fine grid is exact to O(h^6), so
+ * the whole fine grid becomes fourth order.  Cost: a quarter-size solve and two streaming passes.
+ * fp64, one GPU.  Synchronous.  Every step always runs; the stop reasons of the two solves are
+ * reported, never acted on:
+ *   1. The half-resolution context.  Owned by ctx, created on the first call, destroyed by
+ *      pgmg_destroy: pgmg_create on a copy of ctx's config with N' = (N + 1) / 2 and
+ *      h0' = 2 h_0 (h_0: pgmg_config.h0, or a / (N - 1); the doubling is exact, as on the
+ *      context's own level 1), world 1, everything else equal.  Before each call its eps is
+ *      set to ctx's current eps if they differ.
+ *   2. Its problem.  phi' = the injection of the current phi, phi'(j, i) = phi(2j, 2i), the
+ *      whole grid, so its frame is the injected frame; f' = the injection of the level-0
+ *      right-hand side as stored (the caller's f, or the analytic RHS that
+ *      pgmg_set_problem*(.., NULL) keeps).  Both are written on the device.  The child's problem
+ *      is one with a caller's f (nothing regenerated, no PGMG_MON_ERROR); its statistics and
+ *      speculation history start over.
+ *   3. pgmg_fmg_bc(child, nu, omega), then pgmg_solve_damped(child, opts', omega, &info->coarse),
+ *      opts' = opts with monitor = PGMG_MON_RESIDUAL.
+ *   4. pgmg_fmg_bc(ctx, nu, omega), then pgmg_solve_damped(ctx, opts, omega, &info->fine);
+ *      pgmg_history afterwards is this solve's.
+ *   5. The extrapolation, on phi where it lies (the level-0 grid, or the caller's array of
+ *      pgmg_set_problem_device), F = phi (Nf = N points per side), Cg = the child's phi (Nc = N'):
+ *        D(j, i) = (F(2j, 2i) - Cg(j, i)) * K3      0 <= j, i < Nc, frame included; K3 the double
+ *                  nearest 1/3 (0x3FD5555555555555): one rounding for the difference, one for the
+ *                  product (a product, so the result does not depend on how a division is lowered)
+ *        E = C(D)                                   pgmg_fmg's cubic interpolation, its formulas
+ *                                                   and evaluation order
+ *        F(y, x) <- F(y, x) + E(y, x)               1 <= y, x <= Nf - 2, one rounding
+ *      Every D comes from the F of before the operation (two passes: D into a coarse-sized
+ *      scratch grid, allocated on the first call, then the pointwise update); no fused
+ *      multiply-add.  The frame of F is never written: a -0.0 there stays -0.0.
+ * Afterwards phi's frame is bit for bit the one it had and f is untouched.  The entry changes
+ * phi: it drops the carry and resets the speculation history, as pgmg_fmg_bc does.  pgmg_stats of
+ * ctx counts its own FMG and solve; the child's sweeps and early exits are in info.  A later
+ * pgmg_vcycle continues from the extrapolated phi.
+ * What to ask for.  Check 0 of both solves is the FMG iterate, whose residual is already small,
+ * so rtol (relative to check 0) says little: state the target as atol.  The extrapolation needs
+ * both solves converged well below the h^4 it is after, atol ~ 1e-10 ||f||_2; what fp64 can
+ * reach is ||r|| / ||f|| ~ 0.4 N^2 2^-52.  With the default eps = 1e-7 the smoother's early
+ * exits fire at loose tolerances and break the order (atol = 1e-8 ||f||: error ratios 2.9 and
+ * 11.5 instead of 16 at N = 257); with atol = 1e-11 ||f|| the order is intact but the solves take
+ * 18-25 cycles instead of 13-16.  The entry leaves eps alone; eps < 0 (pgmg_config.eps) is
+ * recommended.  The gain is largest where fp64 has room: useful for N <= 2049; at N = 16385 h^4
+ * is below fp64 rounding, the entry runs there and gains nothing.  The model is
+ * tests/extrap_model.py.
+ * Errors, all before anything is enqueued and before a child is created.  PGMG_ERR_ARG: a null
+ * argument; invalid opts (pgmg_solve's rule); nu < 1; omega not finite, <= 0 or > 1; N < 9; a
+ * context or a child whose coarsest level has fewer than 5 points per side.  omega = 0 (the
+ * undamped climb and solve) is refused: the undamped smoother leaves ||r|| / ||f|| at 1e-4 after
+ * 150 V-cycles, and that algebraic error swamps the h^4 term (extrapolated error ratios scatter
+ * between 2.4 and 15).  PGMG_ERR_STATE: before pgmg_set_problem*; world > 1; an fp32 context
+ * (fp32 solves stall at ||r|| / ||f|| ~ 1e-5 .. 1e-3, a rounding floor that leaves the
+ * extrapolated error at 2e-7 .. 2e-6 from N = 65 up: no better than second order);
+ * PGMG_MON_ERROR with a caller's f. */
+typedef struct pgmg_extrap_info {
+    pgmg_solve_info fine, coarse;            /* the two damped solves; check 0 is the FMG iterate */
+    long long coarse_sweeps, coarse_exits;   /* the half-resolution context's pgmg_stats */
+    double extrap_ms;                        /* device time of the two extrapolation passes */
+    double elapsed_ms;                       /* host wall time of the call */
+} pgmg_extrap_info;
+int pgmg_solve_extrap(pgmg_ctx *ctx, const pgmg_solve_opts *o, int nu, double omega,
+                      pgmg_extrap_info *info);
+
 /* Cumulative smoother sweeps and early exits since set_problem.  The sweeps are the
  * oracle's.  The early exits are those that cut a smoother call short: the check after a
  * call's last sweep cannot change the result and is not evaluated, so where the oracle's
@@ -680,6 +747,13 @@ int pgmg_rhs(double *d_f, int W, int H, double h, double a, double p, double q, 
  * partial sums) belongs to the per-stream set below. */
 int pgmg_damp_grid(double *d_x, const double *d_f, int N, double h, double omega, double *res_norm,
                    void *stream);
+/* The extrapolation of pgmg_solve_extrap (step 5 above) on caller-owned device arrays, fp64:
+ * d_fine Nf x Nf, pitch Nf, updated in place on its interior (its frame is never written);
+ * d_coarse Nc x Nc, Nc = (Nf + 1) / 2, pitch Nc, only read.  fine <- fine + C((fine(2j, 2i) -
+ * coarse) * K3), every difference taken from the fine of before the call.  Asynchronous on
+ * `stream`; the coarse-sized scratch grid belongs to the per-stream set below.  Nf not 2^k + 1
+ * with k >= 3, or a null pointer: PGMG_ERR_ARG, nothing enqueued. */
+int pgmg_extrap_grid(double *d_fine, const double *d_coarse, int Nf, void *stream);
 /* The op-level entries keep one scratch set (partial sums, flags, ping-pong buffer) per
  * stream they were called on; this waits for `stream` and frees its set (a later op on the
  * same stream allocates a fresh one).  Call it before destroying a stream the ops used. */

@@ -28,7 +28,7 @@ from ._capi import (PGMG_FLAG_LOOPBACK, PGMG_FLAG_NO_CROSS, PGMG_FLAG_NO_GRAPH,
                     PGMG_MON_RESIDUAL, PGMG_MON_ERROR, PGMG_CYCLE_V, PGMG_CYCLE_W, PGMG_CYCLE_F,
                     PGMG_STOP_CONVERGED, PGMG_STOP_MAX_CYCLES, PGMG_STOP_STALLED,
                     PGMG_STOP_NONFINITE, PgmgMonitorOut, PgmgSolveOpts, PgmgSolveInfo,
-                    check, load)
+                    PgmgExtrapInfo, check, load)
 
 PKG_DIR = pathlib.Path(__file__).resolve().parent
 
@@ -42,7 +42,7 @@ __all__ = [
     "PGMG_FLAG_HOST_TRANSPORT", "HostTransport", "DeviceGrid",
     "PGMG_MON_RESIDUAL", "PGMG_MON_ERROR", "PGMG_CYCLE_V", "PGMG_CYCLE_W", "PGMG_CYCLE_F",
     "PGMG_STOP_CONVERGED", "PGMG_STOP_MAX_CYCLES", "PGMG_STOP_STALLED", "PGMG_STOP_NONFINITE",
-    "PgmgSolveOpts", "PgmgSolveInfo", "PgmgMonitorOut",
+    "PgmgSolveOpts", "PgmgSolveInfo", "PgmgMonitorOut", "PgmgExtrapInfo",
 ]
 
 
@@ -335,7 +335,7 @@ class Solver:
 
     def solve(self, cycle="V", rtol=1e-3, atol=0.0, max_cycles=30, check_every=1,
               stall_ratio=0.0, stall_checks=2, error=False, damp=0.0, start=None, nu=2,
-              boundary="zero"):
+              boundary="zero", order=2):
         """Cycle until the residual norm is at most max(atol, rtol * r0), the cycle cap, a
         stall or a non-finite norm (pgmg_solve; the stop rule: include/pgmg.h).  Returns the
         PgmgSolveInfo with a `.history` list of (cycle, res, rel_error), check 0 first.
@@ -349,10 +349,24 @@ class Solver:
         a solve from zero.
         boundary: passed to fmg with start="fmg": "zero" ignores the current phi, boundary
         included, and solves the zero-boundary problem; "keep" ignores its interior only and
-        solves the problem with the Dirichlet data phi carries (ignored without start)."""
+        solves the problem with the Dirichlet data phi carries (ignored without start).
+        order: 2 is the solve described above.  4 (pgmg_solve_extrap; fp64, one GPU) makes the
+        result fourth-order accurate by Richardson extrapolation: the same damped solve, started
+        from fmg(nu, damp, "keep"), on this grid and on the grid of every second point, then
+        phi <- phi + cubic((phi - phi_2h) / 3) on the interior.  It needs damp > 0 and implies
+        start="fmg" and boundary="keep"; state the target as atol (~1e-10 ||f||) and create the
+        Solver with eps < 0 (include/pgmg.h).  Returns the fine solve's PgmgSolveInfo with
+        `.history`, `.coarse` (the half-resolution solve's PgmgSolveInfo), `.coarse_sweeps`,
+        `.coarse_exits`, `.extrap_ms` (device time of the two extrapolation passes) and
+        `.total_ms` (host wall time of the whole call)."""
         if start not in (None, "fmg"):
             raise ValueError(f"start must be None or 'fmg', not {start!r}")
-        if start == "fmg":
+        if order not in (2, 4):
+            raise ValueError(f"order must be 2 or 4, not {order!r}")
+        if order == 4 and not damp > 0.0:
+            raise ValueError("order=4 needs damp > 0 (0.5 recommended): undamped solves leave an "
+                             "algebraic error above the h^4 term")
+        if start == "fmg" and order == 2:
             self.fmg(nu, damp if damp != 0.0 else None, boundary)
         o = PgmgSolveOpts()
         check(self.lib.pgmg_solve_opts_default(C.byref(o)), "pgmg_solve_opts_default")
@@ -361,6 +375,15 @@ class Solver:
         o.rtol, o.atol, o.max_cycles, o.check_every = rtol, atol, int(max_cycles), int(check_every)
         o.stall_ratio, o.stall_checks = stall_ratio, int(stall_checks)
         o.monitor = PGMG_MON_RESIDUAL | (PGMG_MON_ERROR if error else 0)
+        if order == 4:
+            ex = PgmgExtrapInfo()
+            check(self.lib.pgmg_solve_extrap(self.h, C.byref(o), int(nu), float(damp),
+                                             C.byref(ex)), "pgmg_solve_extrap")
+            info = ex.fine
+            info.coarse, info.coarse_sweeps, info.coarse_exits = ex.coarse, ex.coarse_sweeps, ex.coarse_exits
+            info.extrap_ms, info.total_ms = ex.extrap_ms, ex.elapsed_ms
+            info.history = self.history()
+            return info
         info = PgmgSolveInfo()
         if damp == 0.0:
             check(self.lib.pgmg_solve(self.h, C.byref(o), C.byref(info)), "pgmg_solve")
@@ -612,6 +635,21 @@ class _Ops:
         check(load().pgmg_damp_grid(self._ptr(x), self._ptr(f), N, float(h), float(omega),
                                     C.byref(out) if norm else None, stream), "pgmg_damp_grid")
         return out.value if norm else None
+
+    def extrapolate(self, fine, coarse, stream=None):
+        """fine <- fine + cubic((fine[::2, ::2] - coarse) * K3) on the interior of fine
+        (pgmg_extrap_grid): the Richardson extrapolation of two second-order solutions, fine
+        Nf x Nf and coarse (Nf + 1) / 2 squared float64 device arrays, Nf = 2^k + 1, k >= 3.  The
+        frame of fine is never written.  Asynchronous on `stream`."""
+        Nf, Nc = fine.shape[0], coarse.shape[0]
+        assert tuple(fine.shape) == (Nf, Nf) and tuple(coarse.shape) == (Nc, Nc), (fine.shape, coarse.shape)
+        assert Nf == 2 * Nc - 1, (Nf, Nc)
+        check(load().pgmg_extrap_grid(self._ptr(fine), self._ptr(coarse), Nf, stream),
+              "pgmg_extrap_grid")
+
+    def release(self, stream=None):
+        """Wait for `stream` and free the scratch set the ops keep for it (pgmg_ops_release)."""
+        check(load().pgmg_ops_release(stream), "pgmg_ops_release")
 
     def rhs(self, f, h, a=1.0, p=1.0, q=1.0, stream=None):
         H, W = f.shape

@@ -114,6 +114,12 @@ class PgmgSolveInfo(C.Structure):
                 ("elapsed_ms", C.c_double)]
 
 
+class PgmgExtrapInfo(C.Structure):
+    _fields_ = [("fine", PgmgSolveInfo), ("coarse", PgmgSolveInfo),
+                ("coarse_sweeps", C.c_longlong), ("coarse_exits", C.c_longlong),
+                ("extrap_ms", C.c_double), ("elapsed_ms", C.c_double)]
+
+
 # (name, restype, argtypes) for every symbol include/pgmg.h declares
 _P = C.c_void_p
 _DP = C.POINTER(C.c_double)
@@ -149,6 +155,8 @@ SIGNATURES = [
     ("pgmg_fmg_damped", C.c_int, [_P, C.c_int, C.c_double]),
     ("pgmg_fmg_bc", C.c_int, [_P, C.c_int, C.c_double]),
     ("pgmg_fmg_interp_time", C.c_int, [_P, C.c_int, _DP, _DP]),
+    ("pgmg_solve_extrap", C.c_int, [_P, C.POINTER(PgmgSolveOpts), C.c_int, C.c_double,
+                                    C.POINTER(PgmgExtrapInfo)]),
     ("pgmg_stats", C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     ("pgmg_stats_detail", C.c_int, [_P, C.POINTER(C.c_longlong)]),
     ("pgmg_last_elapsed_ms", C.c_int, [_P, _DP]),
@@ -183,6 +191,7 @@ SIGNATURES = [
     ("pgmg_rhs", C.c_int, [_P, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
                            _P]),
     ("pgmg_damp_grid", C.c_int, [_P, _P, C.c_int, C.c_double, C.c_double, _DP, _P]),
+    ("pgmg_extrap_grid", C.c_int, [_P, _P, C.c_int, _P]),
     ("pgmg_ops_release", C.c_int, [_P]),
     ("pgmg_device_alloc", C.c_int, [C.POINTER(_P), C.c_size_t]),
     ("pgmg_device_free", C.c_int, [_P]),

@@ -250,6 +250,13 @@ struct pgmg_ctx {
     // phi at the time of the call, 4 N elements of the context's type -- row 0, row N-1,
     // column 0, column N-1
     void *fmg_frame = nullptr;
+    // pgmg_solve_extrap (pgmg_extrap.hip), made on its first call: the half-resolution context
+    // this one owns, the coarse-sized scratch grid D of the extrapolation (a registered
+    // allocation; element (0, 0) at ex_D + kOff, pitch pitch_for(Nc)) and the events around its
+    // two passes
+    pgmg_ctx *ex_child = nullptr;
+    double *ex_D = nullptr;
+    hipEvent_t ex_ev0 = nullptr, ex_ev1 = nullptr;
 };
 
 namespace pgmg {

@@ -30,6 +30,8 @@
 //                    stop rule itself is the HIP-free pgmg_stop.h
 //   pgmg_fmg.hip     full multigrid for the problem's own f: the cubic interpolation pass (its
 //                    kernel too), the restricted f chain, the climb, pgmg_fmg
+//   pgmg_extrap.hip  fourth-order solves: the half-resolution context, the injection and the two
+//                    extrapolation passes (their kernels too), pgmg_solve_extrap
 #include <cxxabi.h>
 
 #include <cmath>
@@ -131,6 +133,13 @@ int pgmg_destroy(pgmg_ctx *c)
         unregister_alloc(c->fmg_frame);
         (void)hipFree(c->fmg_frame);
     }
+    if (c->ex_child) (void)pgmg_destroy(c->ex_child);
+    if (c->ex_D) {
+        unregister_alloc(c->ex_D);
+        (void)hipFree(c->ex_D);
+    }
+    if (c->ex_ev0) (void)hipEventDestroy(c->ex_ev0);
+    if (c->ex_ev1) (void)hipEventDestroy(c->ex_ev1);
     if (c->fmg_tab) (void)hipFree(c->fmg_tab);
     if (c->flags) (void)hipFree(c->flags);
     if (c->stats) (void)hipFree(c->stats);
@@ -543,6 +552,40 @@ int pgmg_problem_device_info(pgmg_ctx *c, int *bound, int *inplace)
 }
 
 }  // extern "C"
+
+// A problem from device grids (pgmg_solve_extrap's half-resolution problem): phi and f of the
+// fp64, one-GPU context c become the injections phi(j, i) = phi_src(2j, 2i), f(j, i) =
+// f_src(2j, 2i) of two device arrays with pitches Pphi and Pf, written on stream s (the stream
+// that produced the sources; c's own is idle and waited for) into c's level-0 grids, phi's frame
+// mirrored into B and S as pgmg_set_problem does.  The problem is one with a caller's f: nothing
+// is regenerated in-kernel and it has no analytic solution.  Returns after s has finished, with
+// the statistics and the speculation history reset.
+int pgmg::set_problem_injected(pgmg_ctx *c, const double *phi_src, long long Pphi,
+                               const double *f_src, long long Pf, hipStream_t s)
+{
+    if (c->fp32 || c->comm) return set_err(PGMG_ERR_STATE, "injected problem: fp64, one GPU only");
+    Level &L = c->lv[0];
+    const int N = L.N;
+    PGMG_TRY(stream_wait(c));
+    PGMG_TRY(check_span(G<double>(L.A), L.P, 8, 0, N - 1, 0, N - 1, "injected problem phi"));
+    PGMG_TRY(check_span(G<double>(L.F), L.P, 8, 0, N - 1, 0, N - 1, "injected problem f"));
+    c->ext_phi = nullptr;
+    c->ext_f = nullptr;
+    launch_inject(phi_src, Pphi, G<double>(L.A), L.P, N, s);
+    launch_inject(f_src, Pf, G<double>(L.F), L.P, N, s);
+    HIPC(hipGetLastError());
+    // (rows 0 .. N of a level-0 grid are one contiguous range: see pgmg_set_problem)
+    const size_t bytes = (size_t)L.P * L.es * (size_t)N;
+    for (const Grid *g : {&L.B, &c->S})
+        if (g->base)
+            HIPC(hipMemcpyAsync(row_ptr(*g, 0, L.P, L.es), row_ptr(L.A, 0, L.P, L.es), bytes,
+                                hipMemcpyDeviceToDevice, s));
+    HIPC(hipStreamSynchronize(s));
+    c->gen_rhs = false;
+    c->rgfx = c->rgsy = nullptr;
+    c->analytic = false;
+    return problem_reset(c);
+}
 
 // ---------------------------------------------------------------------------
 // Device-resident problems (pgmg_set_problem_device): the reference's contract.

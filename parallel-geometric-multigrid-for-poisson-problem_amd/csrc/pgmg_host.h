@@ -81,6 +81,9 @@ void sine_tables(const pgmg_config &cfg, int N, double h, std::vector<double> &s
 int order_after_caller(pgmg_ctx *c);
 int ext_stage_in(pgmg_ctx *c, bool inplace);
 int ext_stage_out(pgmg_ctx *c);
+// phi and f of c <- the injections (every second row and column) of two device arrays
+int set_problem_injected(pgmg_ctx *c, const double *phi_src, long long Pphi, const double *f_src,
+                         long long Pf, hipStream_t s);
 
 // --- pgmg_monitor.hip
 // the damping pass on a level of the FMG pyramid (no norm, nothing waits); fmg_damp_reserve

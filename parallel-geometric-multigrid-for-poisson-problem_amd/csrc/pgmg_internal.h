@@ -299,4 +299,13 @@ void launch_damp_grid(T *x, long long Px, const T *f, long long Pf, int N, doubl
                       double omega, const double *gfx, const double *gsy, double *partials, T *side,
                       double *sums, hipStream_t s);
 
+// Richardson extrapolation (pgmg_extrap.hip; include/pgmg.h "Fourth-order solves"), fp64.
+// launch_inject: dst(j, i) = src(2j, 2i) on n x n destination points.  launch_extrap: the two
+// passes fine <- fine + C((fine(2j, 2i) - coarse) * K3) on a fine grid of 2 Nc - 1 points per
+// side; D: Nc x Nc scratch, pitch Pd.  No span checks here: the callers check the arrays that
+// are the library's (a caller's own array is not a registered allocation).
+void launch_inject(const double *src, long long Ps, double *dst, long long Pd, int n, hipStream_t s);
+void launch_extrap(double *fine, long long Pf, const double *coarse, long long Pc, double *D,
+                   long long Pd, int Nc, hipStream_t s);
+
 }  // namespace pgmg

@@ -36,6 +36,8 @@ struct OpScratch {
     size_t side_elems = 0;
     double *mon = nullptr;    // pgmg_damp_grid: 3 partial sums per workgroup, then the 3 totals
     size_t mon_elems = 0;
+    double *exd = nullptr;    // pgmg_extrap_grid: the coarse-sized difference grid D
+    size_t exd_elems = 0;
 };
 
 // One scratch set per stream: ops enqueued on different streams never share partial sums,
@@ -98,9 +100,41 @@ int ensure_mon(hipStream_t s, OpScratch &o, size_t elems)
     return PGMG_OK;
 }
 
+int ensure_exd(hipStream_t s, OpScratch &o, size_t elems)
+{
+    std::lock_guard<std::mutex> lk(g_op_mu);
+    if (elems <= o.exd_elems) return PGMG_OK;
+    if (o.exd) {
+        HIPC(hipStreamSynchronize(s));
+        HIPC(hipFree(o.exd));
+    }
+    o.exd = nullptr;
+    o.exd_elems = 0;
+    HIPC(hipMalloc((void **)&o.exd, elems * sizeof(double)));
+    o.exd_elems = elems;
+    return PGMG_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+// fine <- fine + C((fine(2j, 2i) - coarse) * K3) on the caller's arrays (pitches Nf and Nc): the
+// two passes of pgmg_solve_extrap's extrapolation (pgmg_extrap.hip), D dense in the stream's set
+int pgmg_extrap_grid(double *d_fine, const double *d_coarse, int Nf, void *stream)
+{
+    if (!d_fine || !d_coarse || Nf < 9 || ((Nf - 1) & (Nf - 2)) != 0)
+        return set_err(PGMG_ERR_ARG, "pgmg_extrap_grid: need fine, coarse, Nf = 2^k + 1 with k >= 3");
+    const int Nc = (Nf + 1) / 2;
+    hipStream_t s = (hipStream_t)stream;
+    OpScratch *op = nullptr;
+    int e = ensure_scratch(s, 0, &op);
+    if (e) return e;
+    if ((e = ensure_exd(s, *op, (size_t)Nc * Nc))) return e;
+    launch_extrap(d_fine, Nf, d_coarse, Nc, op->exd, Nc, Nc, s);
+    HIPC(hipGetLastError());
+    return PGMG_OK;
+}
 
 // One damping pass x <- x + w r on the caller's arrays (pitch N): the level-general launch of
 // the context's damping pass (pgmg_monitor.hip), its decomposition and sums those of a context
@@ -300,7 +334,7 @@ int pgmg_ops_release(void *stream)
     }
     HIPC(hipStreamSynchronize(s));   // ops still queued on s may use the set
     for (void *p : {(void *)o.partials, (void *)o.flags, (void *)o.stats, (void *)o.scalar,
-                    (void *)o.tmp, (void *)o.side, (void *)o.mon})
+                    (void *)o.tmp, (void *)o.side, (void *)o.mon, (void *)o.exd})
         if (p) HIPC(hipFree(p));
     return PGMG_OK;
 }
