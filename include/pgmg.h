@@ -425,6 +425,13 @@ int pgmg_history(pgmg_ctx *ctx, int cap, int *cycle, double *res, double *rel_er
  * omega = 1/2).  pgmg_history records the r_i; with PGMG_MON_ERROR rel_error is that of the
  * pre-update iterate (the same pass sums it).  Chunks after a damp start uncarried.
  *
+ * Tested off the defaults, bitwise against tests/damp_model.py at the context's own mesh width
+ * (tests/test_gpu_late_params.py): the pass with a = -2, 1e-3 .. 1000, negative, zero and
+ * non-integer p, q and h0 = 0.7 / (N - 1), 1 / N, with the analytic f regenerated, with
+ * PGMG_FLAG_STORED_RHS and with a caller's f, fp64 and fp32, context-owned and device-bound;
+ * the solve with V-cycles, W-cycles at alpha 1, 2 and 4, F-cycles, check_every 2, PGMG_MON_ERROR
+ * at a caller's h0, n_coarse 9 and tail_n 17.
+ *
  * pgmg_damp_time: `reps` damping passes (the pass, the scatter of its deferred edges and the
  * reduction each) back to back between two hipEvents, after two warm ones; mean device ms per
  * pass and its algorithmic bytes (the monitor's model + one element per interior point
@@ -501,7 +508,11 @@ int pgmg_fmg(pgmg_ctx *ctx, int nu);
  * wait for nothing.  Every early-exit check is decided in-stream; the sweep and early-exit
  * statistics are those of the cycles alone.  It drops the carry and resets the speculation
  * history.  f is left untouched.  The damping pass's side buffer is allocated on the first
- * call. */
+ * call.  Tested off the defaults, bitwise against tests/fmg_damped_model.py with h_l = h0 * 2^l
+ * (tests/test_gpu_late_params.py): a = -2, 1e-3 .. 1000, asymmetric, negative and non-integer
+ * p, q, h0 = 0.7 / (N - 1) and 1 / N, n_coarse 9, 17 and 1000 (no climb), coarse_iter 0 and 30,
+ * (v1, v2) = (2, 3), tail_n 9 and 17, a cross-fused level 0, the analytic f regenerated on
+ * level 0 and PGMG_FLAG_STORED_RHS, a caller's f, fp64 and fp32. */
 int pgmg_fmg_damped(pgmg_ctx *ctx, int nu, double omega);
 /* ---- Full multigrid with Dirichlet data -------------------------------------------------
  * pgmg_fmg and pgmg_fmg_damped start from u_L = 0 and end with a zero boundary: a problem whose
@@ -535,7 +546,10 @@ int pgmg_fmg_damped(pgmg_ctx *ctx, int nu, double omega);
  * continue and are the model's.  It drops the carry and resets the speculation history.  A later
  * pgmg_vcycle / pgmg_wcycle / pgmg_solve continues from u_0 and keeps its frame.  The frame
  * buffer (4 N elements) is allocated on the first call.  Cost over pgmg_fmg: the frame's save, a
- * fill of the coarsest grid and one to five launches of O(N_l) elements per level. */
+ * fill of the coarsest grid and one to five launches of O(N_l) elements per level.  Tested off
+ * the defaults with omega 0 and 1/2 on the parameter values listed for pgmg_fmg_damped, the frame
+ * being the exact solution's (of order one on the far boundary for non-integer p, q or a
+ * caller's h0) or random (tests/test_gpu_late_params.py). */
 int pgmg_fmg_bc(pgmg_ctx *ctx, int nu, double omega);
 /* Measurement: `reps` cubic interpolation passes level 1 -> level 0 back to back on the
  * context's stream between two hipEvents, after two warm ones; mean device ms per pass and its
@@ -553,10 +567,12 @@ int pgmg_fmg_interp_time(pgmg_ctx *ctx, int reps, double *ms_per_pass, double *b
  * fp64, one GPU.  Synchronous.  Every step always runs; the stop reasons of the two solves are
  * reported, never acted on:
  *   1. The half-resolution context.  Owned by ctx, created on the first call, destroyed by
- *      pgmg_destroy: pgmg_create on a copy of ctx's config with N' = (N + 1) / 2 and
- *      h0' = 2 h_0 (h_0: pgmg_config.h0, or a / (N - 1); the doubling is exact, as on the
- *      context's own level 1), world 1, everything else equal.  Before each call its eps is
- *      set to ctx's current eps if they differ.
+ *      pgmg_destroy: pgmg_create on a copy of ctx's config with N' = (N + 1) / 2 and a mesh
+ *      width of 2 h_0 (h_0: pgmg_config.h0, or a / (N - 1); the doubling is exact, as on the
+ *      context's own level 1), world 1, everything else equal.  The copy's h0 is 2 * h0 where
+ *      the caller gave one and stays 0 otherwise: a / (N' - 1) is 2 (a / (N - 1)) bit for bit,
+ *      also for a < 0, where the mesh width is negative and could not be stated as an h0.
+ *      Before each call its eps is set to ctx's current eps if they differ.
  *   2. Its problem.  phi' = the injection of the current phi, phi'(j, i) = phi(2j, 2i), the
  *      whole grid, so its frame is the injected frame; f' = the injection of the level-0
  *      right-hand side as stored (the caller's f, or the analytic RHS that
@@ -591,7 +607,11 @@ int pgmg_fmg_interp_time(pgmg_ctx *ctx, int reps, double *ms_per_pass, double *b
  * 18-25 cycles instead of 13-16.  The entry leaves eps alone; eps < 0 (pgmg_config.eps) is
  * recommended.  The gain is largest where fp64 has room: useful for N <= 2049; at N = 16385 h^4
  * is below fp64 rounding, the entry runs there and gains nothing.  The model is
- * tests/extrap_model.py.
+ * tests/extrap_model.py.  Tested off the defaults, bitwise against it (tests/
+ * test_gpu_late_params.py): a = -2, 3 and 1000, asymmetric and non-integer p, q, h0 =
+ * 0.7 / (N - 1) and 1 / N (the child then runs at an h0' that is not 1 / (N' - 1)), n_coarse 9,
+ * coarse_iter 0, (v1, v2) = (2, 3), and N = 129 with tail_n = 17, where the child has bulk
+ * levels of its own; context-owned and device-bound, staged and in place.
  * Errors, all before anything is enqueued and before a child is created.  PGMG_ERR_ARG: a null
  * argument; invalid opts (pgmg_solve's rule); nu < 1; omega not finite, <= 0 or > 1; N < 9; a
  * context or a child whose coarsest level has fewer than 5 points per side.  omega = 0 (the

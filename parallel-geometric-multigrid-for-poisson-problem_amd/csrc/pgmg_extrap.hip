@@ -224,11 +224,21 @@ static int extrap_setup(pgmg_ctx *c)
     if (!c->ex_child) {
         pgmg_config cfg = c->cfg;
         cfg.N = Nc;
-        cfg.h0 = 2 * c->lv[0].h;   // (lv[0].h is cfg.h0, or a / (N - 1))
+        // the child's mesh width is 2 * lv[0].h: the caller's h0 doubled, or (h0 = 0) left to
+        // pgmg_create's a / (Nc - 1) = 2 * (a / (N - 1)) bit for bit (Nc - 1 = (N - 1) / 2; a
+        // factor of two commutes with the division's rounding).  Not 2 * lv[0].h outright: with
+        // a < 0 that is negative, and pgmg_create refuses a negative h0
+        cfg.h0 = c->cfg.h0 > 0.0 ? 2 * c->cfg.h0 : 0.0;
         cfg.rank = 0;
         cfg.world = 1;
         cfg.nccl_unique_id = nullptr;
         PGMG_TRY(pgmg_create(&c->ex_child, &cfg));
+        if (c->ex_child->lv[0].h != 2 * c->lv[0].h) {   // (an a at the edge of the double range)
+            pgmg_destroy(c->ex_child);
+            c->ex_child = nullptr;
+            return set_err(PGMG_ERR_STATE, "pgmg_solve_extrap: the half-resolution context's mesh "
+                                           "width is not twice the context's");
+        }
     }
     if (!c->ex_D) {
         const size_t bytes = alloc_elems(Nc, Nc) * sizeof(double);

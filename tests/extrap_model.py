@@ -7,7 +7,9 @@ extrapolate(fine, coarse):
     fine[1:-1, 1:-1] + E[1:-1, 1:-1]       one rounding; the frame of fine is kept
 solve_extrap(...): on the grid and on the grid of every second point (phi0[::2, ::2], f[::2, ::2],
     2 h) fmg_bc_model.fmg_bc(nu, omega), then damp_model.solve_damped(omega) from it; the two
-    results extrapolated.  a = 1 (h = 1 / (N - 1), as damp_model.solve_damped takes it).
+    results extrapolated.  The fine solve runs at the context's mesh width h0 (None: a / (N - 1)),
+    the half-resolution one at 2 h0 (exact), both with the same oracle fields (a, p, q, alpha,
+    n_coarse, coarse_iter, v1, v2): pgmg_solve_extrap copies the parent's configuration.
 """
 from types import SimpleNamespace
 
@@ -35,24 +37,28 @@ def extrapolate(fine, coarse):
     return out
 
 
-def _solve(N, f, phi0, nu, omega, eps, rule):
-    o = oracle.Oracle(eps=eps)
-    u = fmg_bc_model.fmg_bc(o, phi0, f, nu, omega)
-    r = damp_model.solve_damped(N, f=f, phi0=u, omega=omega, eps=eps, **rule)
+def _solve(N, f, phi0, nu, omega, eps, h0, okw, rule):
+    o = oracle.Oracle(eps=eps, **okw)
+    u = fmg_bc_model.fmg_bc(o, phi0, f, nu, omega, h0=h0)
+    r = damp_model.solve_damped(N, f=f, phi0=u, omega=omega, eps=eps, h0=h0, **okw, **rule)
     r.sweeps += o.sweeps            # the context's statistics continue from the FMG's
     r.exits = o.cut_exits + r.oracle.cut_exits
     return r
 
 
-def solve_extrap(N, f, phi0, nu=2, omega=0.5, eps=1e-7, **rule):
-    """pgmg_solve_extrap on (f, phi0), both (N, N) float64, left untouched.  Returns a namespace:
+def solve_extrap(N, f, phi0, nu=2, omega=0.5, eps=1e-7, h0=None, a=1.0, p=1.0, q=1.0, alpha=3,
+                 n_coarse=5, coarse_iter=10, v1=1, v2=1, **rule):
+    """pgmg_solve_extrap on (f, phi0), both (N, N) float64, left untouched, on a context with the
+    mesh width h0 (None: a / (N - 1)) and the oracle's fields a .. v2.  Returns a namespace:
     phi (the extrapolated solution), phi2 (the fine second-order solution it was made from),
-    fine and coarse (damp_model.solve_damped's namespaces, sweeps including the FMG's)."""
+    fine and coarse (damp_model.solve_damped's namespaces, sweeps and exits including the FMG's)."""
     f = np.ascontiguousarray(f, dtype=np.float64)
     phi0 = np.ascontiguousarray(phi0, dtype=np.float64)
+    okw = dict(a=a, p=p, q=q, alpha=alpha, n_coarse=n_coarse, coarse_iter=coarse_iter, v1=v1, v2=v2)
+    h = a / (N - 1) if h0 is None else h0
     Nc = (N + 1) // 2
     coarse = _solve(Nc, np.ascontiguousarray(f[::2, ::2]), np.ascontiguousarray(phi0[::2, ::2]),
-                    nu, omega, eps, rule)
-    fine = _solve(N, f, phi0, nu, omega, eps, rule)
+                    nu, omega, eps, 2 * h, okw, rule)
+    fine = _solve(N, f, phi0, nu, omega, eps, h, okw, rule)
     return SimpleNamespace(phi=extrapolate(fine.phi, coarse.phi), phi2=fine.phi, fine=fine,
                            coarse=coarse)
