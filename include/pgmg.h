@@ -630,6 +630,54 @@ typedef struct pgmg_extrap_info {
 int pgmg_solve_extrap(pgmg_ctx *ctx, const pgmg_solve_opts *o, int nu, double omega,
                       pgmg_extrap_info *info);
 
+/* ---- Gradient of the solution ------------------------------------------------------------
+ * pgmg_gradient(ctx, order, scale, d_gx, d_gy, norm): both components of scale * grad(phi) of the
+ * current phi on all N x N points, frame included, from one read of phi where it lies (the
+ * context's level-0 grid, or the caller's bound array of pgmg_set_problem_device: nothing is
+ * staged).  h is the context's finest mesh width (pgmg_config.h0, or a / (N - 1); negative for
+ * a < 0), T its element type.  Every expression is evaluated left to right as written, one
+ * rounding per operation, no fused multiply-add.  The frame uses one-sided stencils of the same
+ * order.  Along one line v[0 .. n-1], n = N >= 5:
+ *   order 2:  w = (T)(scale * 0.5 / h)                  the double expression, left to right, then
+ *                                                       converted
+ *     g[k]   = (v[k+1] - v[k-1]) * w                                          1 <= k <= n-2
+ *     g[0]   = (4.0 * v[1] - 3.0 * v[0] - v[2]) * w
+ *     g[n-1] = (3.0 * v[n-1] - 4.0 * v[n-2] + v[n-3]) * w
+ *   order 4:  w = (T)(scale / (12.0 * h))
+ *     g[k]   = (8.0 * (v[k+1] - v[k-1]) - (v[k+2] - v[k-2])) * w              2 <= k <= n-3
+ *     g[0]   = (48.0 * v[1] - 25.0 * v[0] - 36.0 * v[2] + 16.0 * v[3] - 3.0 * v[4]) * w
+ *     g[1]   = (18.0 * v[2] - 10.0 * v[1] - 3.0 * v[0] - 6.0 * v[3] + v[4]) * w
+ *     g[n-1] = (25.0 * v[n-1] - 48.0 * v[n-2] + 36.0 * v[n-3] - 16.0 * v[n-4] + 3.0 * v[n-5]) * w
+ *     g[n-2] = (10.0 * v[n-2] - 18.0 * v[n-3] + 3.0 * v[n-1] + 6.0 * v[n-4] - v[n-5]) * w
+ * gx(y, .) is this along x on every row y, gy(., x) along y on every column x, frame rows and
+ * columns included.  scale = -1 gives E = -grad(phi).  d_gx and d_gy are caller-owned device
+ * arrays of N x N doubles at pitch N; an fp32 context computes in fp32 (a bound array's doubles
+ * converted on load, as pgmg_monitor reads them) and stores the values widened.  Either output
+ * may be NULL: the other component alone is computed and summed.  norm (may be NULL) receives
+ * sqrt(sum gx^2 + gy^2) over all points that were computed, every term the T value widened to
+ * double, squared and summed in double, deterministic by the monitor's scheme: per-workgroup
+ * partials in a fixed lane and row order, added in index order by a second launch, no
+ * floating-point atomics, the decomposition a function of N alone; it agrees with the
+ * sequential sum within N^2 * 2^-52 relative.  Synchronous.  The entry only reads the problem:
+ * it keeps the carry, the speculation history and every statistic, like pgmg_monitor.  fp64 and
+ * fp32 contexts.
+ * Which order.  The field of a second-order solution is second order whatever the stencil, and
+ * the second-order field of a fourth-order solution is second order too: order 4 only pays on
+ * the result of pgmg_solve_extrap, where the field error falls by 16 per doubling of N and is
+ * 2.5e3 to 4e4 times below the second-order pair's at N = 257 (tests/test_grad_cpu.py).  The
+ * model is tests/grad_model.py.
+ * PGMG_ERR_ARG, nothing enqueued and nothing written: a null context, an order other than 2 or 4,
+ * a non-finite scale, both outputs NULL, an output that is not device memory, an output range
+ * that overlaps the other output or phi.  PGMG_ERR_STATE, likewise: before pgmg_set_problem*;
+ * world > 1 -- one GPU only, like pgmg_damp.
+ * pgmg_gradient_time: `reps` passes (order 2 or 4, scale 1, both components and the norm: both
+ * launches each) back to back between two hipEvents, after two warm ones, into two context-owned
+ * output arrays allocated on the first call (16 N^2 bytes); mean device ms per pass and its
+ * algorithmic bytes N^2 * (elem + 16), elem the bytes of a phi element as read (8, or 4 on the
+ * grid of an fp32 context).  Leaves phi as it was. */
+int pgmg_gradient(pgmg_ctx *ctx, int order, double scale, double *d_gx, double *d_gy, double *norm);
+int pgmg_gradient_time(pgmg_ctx *ctx, int order, int reps, double *ms_per_pass, double *bytes);
+
 /* Cumulative smoother sweeps and early exits since set_problem.  The sweeps are the
  * oracle's.  The early exits are those that cut a smoother call short: the check after a
  * call's last sweep cannot change the result and is not evaluated, so where the oracle's
@@ -774,6 +822,16 @@ int pgmg_damp_grid(double *d_x, const double *d_f, int N, double h, double omega
  * `stream`; the coarse-sized scratch grid belongs to the per-stream set below.  Nf not 2^k + 1
  * with k >= 3, or a null pointer: PGMG_ERR_ARG, nothing enqueued. */
 int pgmg_extrap_grid(double *d_fine, const double *d_coarse, int Nf, void *stream);
+/* pgmg_gradient (above) on caller-owned device arrays, fp64: d_phi N x N at pitch N, only read;
+ * d_gx, d_gy N x N doubles at pitch N, either may be NULL.  N = 2^k + 1 with k >= 2; h finite and
+ * not 0 (negative is legal).  norm == NULL: asynchronous on `stream`; otherwise synchronous, and
+ * *norm is bit for bit pgmg_gradient's on a context of that N and h (the decomposition is a
+ * function of N alone); the partial sums belong to the per-stream set below.  Another N, h of 0
+ * or not finite, an order other than 2 or 4, a non-finite scale, a null phi, both outputs NULL,
+ * an output that is not device memory or that overlaps the other output or phi: PGMG_ERR_ARG,
+ * nothing enqueued. */
+int pgmg_gradient_grid(const double *d_phi, double *d_gx, double *d_gy, int N, double h, int order,
+                       double scale, double *norm, void *stream);
 /* The op-level entries keep one scratch set (partial sums, flags, ping-pong buffer) per
  * stream they were called on; this waits for `stream` and frees its set (a later op on the
  * same stream allocates a fresh one).  Call it before destroying a stream the ops used. */

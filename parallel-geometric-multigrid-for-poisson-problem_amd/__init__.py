@@ -393,6 +393,40 @@ class Solver:
         info.history = self.history()
         return info
 
+    def gradient(self, order=4, scale=1.0, gx=None, gy=None, norm=False):
+        """scale * grad(phi) of the current phi on all N x N points, frame included, in one pass
+        over phi where it lies (pgmg_gradient): central differences of the given order (2 or 4)
+        and one-sided ones of the same order on the frame.  scale=-1 gives E = -grad(phi).
+        Order 4 only pays on the result of solve(order=4): the field of a second-order solution
+        is second order whatever the stencil.  gx, gy: N x N float64 CUDA tensors (allocated when
+        None).  Returns (gx, gy), or (gx, gy, sqrt(sum gx^2 + gy^2)) with norm=True.  Only reads
+        the problem: keeps the carry and the statistics.  fp64 and fp32 contexts (an fp32 context
+        computes in fp32 and stores the values widened); one GPU only."""
+        import torch
+        N = self.N
+        dev = torch.device("cuda", int(self.cfg.device))
+        if gx is None:
+            gx = torch.empty((N, N), dtype=torch.float64, device=dev)
+        if gy is None:
+            gy = torch.empty((N, N), dtype=torch.float64, device=dev)
+        for t in (gx, gy):
+            if not (t.is_cuda and t.dtype == torch.float64 and tuple(t.shape) == (N, N)
+                    and t.is_contiguous()):
+                raise ValueError("gx and gy must be contiguous N x N float64 CUDA tensors")
+        out = C.c_double()
+        check(self.lib.pgmg_gradient(self.h, int(order), float(scale), _dptr(gx), _dptr(gy),
+                                     C.byref(out) if norm else None), "pgmg_gradient")
+        return (gx, gy, out.value) if norm else (gx, gy)
+
+    def gradient_time(self, order=4, reps=20):
+        """(mean device ms, algorithmic bytes) of one gradient pass, both components and the
+        norm, over `reps` back to back into context-owned outputs (pgmg_gradient_time;
+        measurement)."""
+        ms, b = C.c_double(), C.c_double()
+        check(self.lib.pgmg_gradient_time(self.h, int(order), int(reps), C.byref(ms), C.byref(b)),
+              "pgmg_gradient_time")
+        return ms.value, b.value
+
     def history(self):
         """The last solve's checks: [(cycles run before the check, res, rel_error), ...]."""
         n = C.c_int()
@@ -646,6 +680,25 @@ class _Ops:
         assert Nf == 2 * Nc - 1, (Nf, Nc)
         check(load().pgmg_extrap_grid(self._ptr(fine), self._ptr(coarse), Nf, stream),
               "pgmg_extrap_grid")
+
+    def gradient(self, phi, h, gx=None, gy=None, order=4, scale=1.0, stream=None, norm=False):
+        """(gx, gy) = scale * grad(phi) on N x N float64 device arrays (pgmg_gradient_grid;
+        N = 2^k + 1, k >= 2; h finite and not 0), the outputs allocated when both are None; pass
+        one of them to compute that component alone (the other is returned as None).  norm=True:
+        returns (gx, gy, sqrt(sum gx^2 + gy^2)) (synchronous); otherwise asynchronous on
+        `stream`."""
+        import torch
+        N = phi.shape[0]
+        assert tuple(phi.shape) == (N, N), phi.shape
+        if gx is None and gy is None:
+            gx, gy = torch.empty_like(phi), torch.empty_like(phi)
+        for t in (gx, gy):
+            assert t is None or tuple(t.shape) == (N, N), t.shape
+        out = C.c_double()
+        check(load().pgmg_gradient_grid(self._ptr(phi), self._ptr(gx), self._ptr(gy), N, float(h),
+                                        int(order), float(scale), C.byref(out) if norm else None,
+                                        stream), "pgmg_gradient_grid")
+        return (gx, gy, out.value) if norm else (gx, gy)
 
     def release(self, stream=None):
         """Wait for `stream` and free the scratch set the ops keep for it (pgmg_ops_release)."""

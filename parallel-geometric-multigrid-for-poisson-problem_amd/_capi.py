@@ -157,6 +157,8 @@ SIGNATURES = [
     ("pgmg_fmg_interp_time", C.c_int, [_P, C.c_int, _DP, _DP]),
     ("pgmg_solve_extrap", C.c_int, [_P, C.POINTER(PgmgSolveOpts), C.c_int, C.c_double,
                                     C.POINTER(PgmgExtrapInfo)]),
+    ("pgmg_gradient", C.c_int, [_P, C.c_int, C.c_double, _P, _P, _DP]),
+    ("pgmg_gradient_time", C.c_int, [_P, C.c_int, C.c_int, _DP, _DP]),
     ("pgmg_stats", C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     ("pgmg_stats_detail", C.c_int, [_P, C.POINTER(C.c_longlong)]),
     ("pgmg_last_elapsed_ms", C.c_int, [_P, _DP]),
@@ -192,6 +194,8 @@ SIGNATURES = [
                            _P]),
     ("pgmg_damp_grid", C.c_int, [_P, _P, C.c_int, C.c_double, C.c_double, _DP, _P]),
     ("pgmg_extrap_grid", C.c_int, [_P, _P, C.c_int, _P]),
+    ("pgmg_gradient_grid", C.c_int, [_P, _P, _P, C.c_int, C.c_double, C.c_int, C.c_double, _DP,
+                                     _P]),
     ("pgmg_ops_release", C.c_int, [_P]),
     ("pgmg_device_alloc", C.c_int, [C.POINTER(_P), C.c_size_t]),
     ("pgmg_device_free", C.c_int, [_P]),

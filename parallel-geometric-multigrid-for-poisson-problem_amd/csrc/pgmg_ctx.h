@@ -257,6 +257,12 @@ struct pgmg_ctx {
     pgmg_ctx *ex_child = nullptr;
     double *ex_D = nullptr;
     hipEvent_t ex_ev0 = nullptr, ex_ev1 = nullptr;
+    // pgmg_gradient (pgmg_gradient.hip): the per-workgroup partial sums of its norm followed by
+    // their total, and pgmg_gradient_time's two output arrays (N * N doubles each, a registered
+    // allocation), both made on the first call that needs them
+    double *grad_buf = nullptr;
+    int grad_cap = 0;             // workgroups grad_buf holds partials for
+    double *grad_out = nullptr;
 };
 
 namespace pgmg {

@@ -138,6 +138,11 @@ int pgmg_destroy(pgmg_ctx *c)
         unregister_alloc(c->ex_D);
         (void)hipFree(c->ex_D);
     }
+    if (c->grad_buf) (void)hipFree(c->grad_buf);
+    if (c->grad_out) {
+        unregister_alloc(c->grad_out);
+        (void)hipFree(c->grad_out);
+    }
     if (c->ex_ev0) (void)hipEventDestroy(c->ex_ev0);
     if (c->ex_ev1) (void)hipEventDestroy(c->ex_ev1);
     if (c->fmg_tab) (void)hipFree(c->fmg_tab);

@@ -308,4 +308,18 @@ void launch_inject(const double *src, long long Ps, double *dst, long long Pd, i
 void launch_extrap(double *fine, long long Pf, const double *coarse, long long Pc, double *D,
                    long long Pd, int Nc, hipStream_t s);
 
+// The gradient pass (pgmg_gradient.hip; include/pgmg.h "Gradient of the solution"): both
+// components of w-scaled differences of x (element (0, 0), pitch Px, read as SX and computed in T)
+// into gx / gy (doubles, pitch N; either may be null).  sum non-null: the pass writes
+// gradient_blocks(N) partial sums to `partials` and one more launch their total to sum[0].  No
+// span checks here (launch_extrap's rule).  gradient_weight: the factor w of an order, scale and
+// mesh width; gradient_arrays_error: what the entries refuse in the caller's arrays.
+int gradient_blocks(int N);
+double gradient_weight(int order, double scale, double h);
+const char *gradient_arrays_error(const void *phi, size_t phi_bytes, const double *gx,
+                                  const double *gy, int N);
+template <class T, class SX>
+void launch_gradient(const SX *x, long long Px, double *gx, double *gy, int N, double w, int order,
+                     double *partials, double *sum, hipStream_t s);
+
 }  // namespace pgmg

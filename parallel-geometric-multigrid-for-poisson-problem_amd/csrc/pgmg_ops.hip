@@ -15,6 +15,7 @@
 #include <cmath>
 #include <map>
 #include <mutex>
+#include <string>
 #include <vector>
 
 #include "pgmg_ctx.h"
@@ -38,6 +39,8 @@ struct OpScratch {
     size_t mon_elems = 0;
     double *exd = nullptr;    // pgmg_extrap_grid: the coarse-sized difference grid D
     size_t exd_elems = 0;
+    double *grad = nullptr;   // pgmg_gradient_grid: a partial sum per workgroup, then the total
+    size_t grad_elems = 0;
 };
 
 // One scratch set per stream: ops enqueued on different streams never share partial sums,
@@ -115,9 +118,55 @@ int ensure_exd(hipStream_t s, OpScratch &o, size_t elems)
     return PGMG_OK;
 }
 
+int ensure_grad(hipStream_t s, OpScratch &o, size_t elems)
+{
+    std::lock_guard<std::mutex> lk(g_op_mu);
+    if (elems <= o.grad_elems) return PGMG_OK;
+    if (o.grad) {
+        HIPC(hipStreamSynchronize(s));
+        HIPC(hipFree(o.grad));
+    }
+    o.grad = nullptr;
+    o.grad_elems = 0;
+    HIPC(hipMalloc((void **)&o.grad, elems * sizeof(double)));
+    o.grad_elems = elems;
+    return PGMG_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+// scale * grad(phi) on the caller's arrays (pitch N): pgmg_gradient's pass (pgmg_gradient.hip),
+// its decomposition and partial sums those of a context of that N
+int pgmg_gradient_grid(const double *d_phi, double *d_gx, double *d_gy, int N, double h, int order,
+                       double scale, double *norm, void *stream)
+{
+    if (!d_phi || N < 5 || ((N - 1) & (N - 2)) != 0 || !std::isfinite(h) || h == 0.0)
+        return set_err(PGMG_ERR_ARG, "pgmg_gradient_grid: need phi, N = 2^k + 1 with k >= 2, a finite "
+                                     "h that is not 0");
+    if ((order != 2 && order != 4) || !std::isfinite(scale))
+        return set_err(PGMG_ERR_ARG, "pgmg_gradient_grid: order must be 2 or 4, scale finite");
+    if (const char *bad = gradient_arrays_error(d_phi, (size_t)N * N * sizeof(double), d_gx, d_gy, N))
+        return set_err(PGMG_ERR_ARG, std::string("pgmg_gradient_grid: ") + bad);
+    hipStream_t s = (hipStream_t)stream;
+    OpScratch *op = nullptr;
+    int e = ensure_scratch(s, 0, &op);
+    if (e) return e;
+    const size_t np = (size_t)gradient_blocks(N);
+    if (norm && (e = ensure_grad(s, *op, np + 1))) return e;
+    double *sum = norm ? op->grad + np : nullptr;
+    launch_gradient<double, double>(d_phi, N, d_gx, d_gy, N, gradient_weight(order, scale, h), order,
+                                    op->grad, sum, s);
+    HIPC(hipGetLastError());
+    if (norm) {
+        double t = 0.0;
+        HIPC(hipMemcpyAsync(&t, sum, sizeof(t), hipMemcpyDeviceToHost, s));
+        HIPC(hipStreamSynchronize(s));
+        *norm = std::sqrt(t);
+    }
+    return PGMG_OK;
+}
 
 // fine <- fine + C((fine(2j, 2i) - coarse) * K3) on the caller's arrays (pitches Nf and Nc): the
 // two passes of pgmg_solve_extrap's extrapolation (pgmg_extrap.hip), D dense in the stream's set
@@ -334,7 +383,7 @@ int pgmg_ops_release(void *stream)
     }
     HIPC(hipStreamSynchronize(s));   // ops still queued on s may use the set
     for (void *p : {(void *)o.partials, (void *)o.flags, (void *)o.stats, (void *)o.scalar,
-                    (void *)o.tmp, (void *)o.side, (void *)o.mon, (void *)o.exd})
+                    (void *)o.tmp, (void *)o.side, (void *)o.mon, (void *)o.exd, (void *)o.grad})
         if (p) HIPC(hipFree(p));
     return PGMG_OK;
 }
