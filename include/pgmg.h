@@ -150,6 +150,12 @@ extern "C" {
 #define PGMG_FLAG_NO_CARRY 131072u /* do not carry the next call's pre-smooth across
                                       pgmg_vcycle calls (the carry: below pgmg_vcycle).  Results
                                       and statistics are identical either way */
+#define PGMG_FLAG_FULL_CHECKS 2097152u /* one GPU: the finest level's cross-cycle pass sums its two
+                                          early-exit checks over every row on speculative calls
+                                          too, instead of over a sample of the rows (a lower
+                                          bound, enough to show that a check cannot fire: below
+                                          pgmg_spec_sampled_info).  Results and statistics are
+                                          identical either way */
 #define PGMG_FLAG_TIME_COMM 262144u /* world > 1: hipEvents around every collective group
                                        (grouped halo exchange, all-to-all, allreduce) on the
                                        context's stream, read by pgmg_comm_stats */
@@ -751,6 +757,17 @@ int pgmg_comm_ranks(pgmg_ctx *ctx, int *ranks);
 /* The carry (above pgmg_vcycle): out[0] calls that started from a carried pre-smooth, out[1]
  * carries made, out[2] carries dropped because their check could fire. */
 int pgmg_carry_info(pgmg_ctx *ctx, long long out[3]);
+
+/* Sampled checks.  On a speculative call (one GPU) the finest level's cross-cycle pass sums
+ * its two early-exit checks over 1 row in 6 (1 in 4 with a caller's f and in the pass that
+ * takes a carry): a lower bound of the full sum, which the validation needs only to show that
+ * the check cannot fire.  A sampled check that could fire rolls the call back like any other and
+ * the rerun decides from full sums; if no cross-cycle check fires then, the context keeps
+ * speculating but its finest passes sum every row from then on, until pgmg_set_problem* or
+ * pgmg_set_eps.  out[0]: finest passes launched in the sampled form; out[1]: rollbacks caused
+ * only by sampled checks after which no such check fired; out[2]: 1 while the context is in that
+ * full-sum mode.  PGMG_FLAG_FULL_CHECKS never samples.  Read-only. */
+int pgmg_spec_sampled_info(pgmg_ctx *ctx, long long out[3]);
 
 /* A new early-exit threshold (JacobiSmoother's eps, Smoother.hpp:38) for the following calls:
  * drops the carry and the speculation history (the statistics continue). */

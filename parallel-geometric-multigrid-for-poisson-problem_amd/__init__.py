@@ -23,7 +23,7 @@ from ._capi import (PGMG_FLAG_LOOPBACK, PGMG_FLAG_NO_CROSS, PGMG_FLAG_NO_GRAPH,
                     PGMG_FLAG_UNFUSED, PGMG_FLAG_NO_RECOMPUTE, PGMG_FLAG_NO_PIN,
                     PGMG_FLAG_NO_R2, PGMG_FLAG_HOST_TRANSPORT, PGMG_FLAG_FAST,
                     PGMG_FLAG_NO_SPEC_FIRE, PGMG_FLAG_NO_CTILE, PGMG_FLAG_NO_CARRY, PGMG_FLAG_TIME_COMM, PGMG_FLAG_NO_SHUFFLE, PGMG_FLAG_NO_SPIN,
-                    PGMG_PROLONG_REFERENCE,
+                    PGMG_FLAG_FULL_CHECKS, PGMG_PROLONG_REFERENCE,
                     PGMG_PROLONG_SYMMETRIC, PGMG_OK, PGMG_ERR_ARG, PGMG_ERR_STATE, PgmgConfig, PgmgError,
                     PGMG_MON_RESIDUAL, PGMG_MON_ERROR, PGMG_CYCLE_V, PGMG_CYCLE_W, PGMG_CYCLE_F,
                     PGMG_STOP_CONVERGED, PGMG_STOP_MAX_CYCLES, PGMG_STOP_STALLED,
@@ -39,7 +39,7 @@ __all__ = [
     "PGMG_PROLONG_SYMMETRIC", "PGMG_PRECISION_FP64", "PGMG_PRECISION_FP32",
     "PGMG_FLAG_STORED_RHS", "PGMG_FLAG_EXACT_DIST", "PGMG_FLAG_SOLO",
     "PGMG_FLAG_NO_RECOMPUTE", "PGMG_FLAG_NO_PIN", "PGMG_FLAG_NO_R2", "PGMG_FLAG_FAST", "PGMG_FLAG_NO_SPEC_FIRE", "PGMG_FLAG_NO_CTILE", "PGMG_FLAG_NO_CARRY", "PGMG_FLAG_TIME_COMM", "PGMG_FLAG_NO_SHUFFLE", "PGMG_FLAG_NO_SPIN",
-    "PGMG_FLAG_HOST_TRANSPORT", "HostTransport", "DeviceGrid",
+    "PGMG_FLAG_HOST_TRANSPORT", "PGMG_FLAG_FULL_CHECKS", "HostTransport", "DeviceGrid",
     "PGMG_MON_RESIDUAL", "PGMG_MON_ERROR", "PGMG_CYCLE_V", "PGMG_CYCLE_W", "PGMG_CYCLE_F",
     "PGMG_STOP_CONVERGED", "PGMG_STOP_MAX_CYCLES", "PGMG_STOP_STALLED", "PGMG_STOP_NONFINITE",
     "PgmgSolveOpts", "PgmgSolveInfo", "PgmgMonitorOut", "PgmgExtrapInfo",
@@ -496,6 +496,13 @@ class Solver:
         """(calls that started from a carried pre-smooth, carries made, carries dropped)."""
         a = (C.c_longlong * 3)()
         check(self.lib.pgmg_carry_info(self.h, a), "pgmg_carry_info")
+        return tuple(a)
+
+    def sampled_info(self):
+        """(finest passes launched with sampled checks, rollbacks caused only by sampled checks
+        after which no cross-cycle check fired, 1 while the context sums every row again)."""
+        a = (C.c_longlong * 3)()
+        check(self.lib.pgmg_spec_sampled_info(self.h, a), "pgmg_spec_sampled_info")
         return tuple(a)
 
     def comm_stats(self):

@@ -42,6 +42,7 @@ PGMG_FLAG_NO_CARRY = 131072
 PGMG_FLAG_TIME_COMM = 262144
 PGMG_FLAG_NO_SHUFFLE = 524288
 PGMG_FLAG_NO_SPIN = 1048576
+PGMG_FLAG_FULL_CHECKS = 2097152
 
 PGMG_PRECISION_FP64 = 0
 PGMG_PRECISION_FP32 = 1
@@ -179,6 +180,7 @@ SIGNATURES = [
     ("pgmg_spec_fire_levels", C.c_int, [_P, C.POINTER(C.c_ulonglong)]),
     ("pgmg_spec_visit_modes", C.c_int, [_P, C.POINTER(C.c_longlong)]),
     ("pgmg_carry_info", C.c_int, [_P, C.POINTER(C.c_longlong)]),
+    ("pgmg_spec_sampled_info", C.c_int, [_P, C.POINTER(C.c_longlong)]),
     ("pgmg_comm_stats", C.c_int, [_P, C.POINTER(C.c_longlong), _DP]),
     ("pgmg_comm_ranks", C.c_int, [_P, C.POINTER(C.c_int)]),
     ("pgmg_set_eps", C.c_int, [_P, C.c_double]),

@@ -63,6 +63,9 @@ struct HaloReq {
 struct SpecHistory {
     bool spec_off = false;        // switched off: a finest-level check fires
     bool fspec_off = false;       // a speculative F call was rolled back: in-stream (problem)
+    // a sampled finest-level check could fire and the full sums then did not: the finest norm is
+    // within ~sqrt(6) of eps, so the finest passes log full sums from now on (still speculative)
+    bool full_sums = false;
     std::vector<char> lvl_exact;  // per bulk level: its checks fire (soon): decide in-stream
     std::vector<char> lvl_fire;   // per bulk level: its checks keep firing: predicted to fire
     std::vector<char> lvl_fire_block;   // a "fires" prediction failed: never again (this problem)
@@ -222,6 +225,9 @@ struct pgmg_ctx {
     // pre-smooth) when no entry touched the problem in between
     bool carry = false;           // lv[1].F holds the validated restriction of lv[0].A's pre-smooth
     long long carry_n[3] = {0, 0, 0};   // calls that took a carry, carries made, dropped
+    // sampled checks (pgmg_postpre_impl.h): finest passes launched in the sampled form; rollbacks
+    // caused only by sampled checks after which no cross-cycle check fired (pgmg_spec_sampled_info)
+    long long sampled_n[2] = {0, 0};
     // the convergence monitor (pgmg_monitor.hip): an analytic problem's unscaled sine tables
     // sx[i], sy[j] of the exact solution (uploaded by setup_rhs beside rhs_tab, zero-padded like
     // it), the per-workgroup partial sums (3 each) followed by the three totals, and the last

@@ -79,6 +79,29 @@ static double *chk_partials(pgmg_ctx *c, int np, int level)
     return chk_mode(c, level) == 0 ? chk_log(c, np, level, 0) : nullptr;
 }
 
+// Sampled checks (pgmg_postpre_impl.h): may the finest pass being enqueued sum its two checks
+// on a sample of its rows?  Only where both are recorded "does not fire" by a speculative V or
+// W call on one GPU, and the context has not fallen back to full sums (pgmg_spec.hip, "sampled
+// checks"); every pass decided in-stream -- k_postpre_decide -- launches the full-sum form.
+static bool pp_sampled(const pgmg_ctx *c)
+{
+    return c->call.lean && !c->call.fspec && c->comm == nullptr && chk_mode(c, 0) == 0 &&
+           !c->hist.full_sums && !(c->cfg.flags & (PGMG_FLAG_FULL_CHECKS | PGMG_FLAG_EXACT_DIST));
+}
+
+// The last n checks logged hold lower bounds of their sums (a sampled pass's): such a check
+// can only be recorded "does not fire".
+static int chk_mark_bound(pgmg_ctx *c, int n)
+{
+    if ((int)c->chks.size() < n) return set_err(PGMG_ERR_STATE, "sampled checks: not logged");
+    for (size_t i = c->chks.size() - n; i < c->chks.size(); ++i) {
+        if (c->chks[i].expect != 0)
+            return set_err(PGMG_ERR_STATE, "sampled checks: a lower bound logged as anything but \"does not fire\"");
+        c->chks[i].bound = 1;
+    }
+    return PGMG_OK;
+}
+
 // ---------------------------------------------------------------------------
 // kernel sequences
 // ---------------------------------------------------------------------------
@@ -686,6 +709,11 @@ static int enqueue_carry_pass(pgmg_ctx *c, CrossState<T> &st, int nq)
     q.partials2 = chk_log(c, nq, 0, 0);
     c->call.carry_chk = (int)c->chks.size() - 1;
     if (q.partials1 == nullptr || q.partials2 == nullptr) return set_err(PGMG_ERR_STATE, "carry pass: check log");
+    if (pp_sampled(c)) {
+        PGMG_TRY(chk_mark_bound(c, 2));
+        q.sampled = 1;
+        ++c->sampled_n[0];
+    }
     const int ev = timed_begin(c, 4);
     PGMG_TRY(launch_postpre(q, c->s));
     PGMG_TRY(timed_end(c, 4, ev));
@@ -786,6 +814,11 @@ static int enqueue_cross_cycles(pgmg_ctx *c, int n, int gamma)
         q.partials1 = lean ? chk_partials(c, nq, 0) : c->partials;
         q.partials2 = lean ? chk_partials(c, nq, 0) : c->partials2;
         q.partials3 = (dist && !lean) ? c->partials3 : nullptr;   // lean: no rare path runs
+        if (pp_sampled(c) && q.partials1 != nullptr && q.partials2 != nullptr) {
+            PGMG_TRY(chk_mark_bound(c, 2));
+            q.sampled = 1;
+            ++c->sampled_n[0];
+        }
         const int slot = q.recompute ? 5 : 3;   // (the recompute form: its own timed slot)
         const int ev = timed_begin(c, slot);
         PGMG_TRY(launch_postpre(q, c->s));

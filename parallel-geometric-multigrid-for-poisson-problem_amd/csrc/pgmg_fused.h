@@ -117,6 +117,10 @@ struct PostPreArgsT {
     // nonzero: XCD-aware tile order (measurement knob PGMG_PP_XCD): the workgroups the hardware
     // places on one XCD (linear id = x mod 8) take a contiguous run of tiles
     int xcd;
+    // nonzero: sampled checks (pgmg_postpre_impl.h): partials1 / partials2 receive the sums of a
+    // sample of the rows, lower bounds of the full sums -- for a speculative call's log only,
+    // never for k_postpre_decide (one GPU: partials3 = nullptr)
+    int sampled;
 };
 
 struct FixArgsF {

@@ -77,6 +77,9 @@ struct CheckRef {
     long long np;
     int level;   // host bookkeeping (per-level speculation policy)
     int expect;  // 0: recorded as "does not fire", 1: as "fires", 2: decided in-stream (norm only)
+    // nonzero: the partials are a lower bound of the check's sum (k_postpre's sampled checks); it
+    // can only show that the check does not fire, so expect is 0 (chk_mark_bound)
+    int bound = 0;
 };
 
 constexpr int kOff = 15;          // doubles between allocation base and element (0,0) (fp64)

@@ -17,7 +17,8 @@
 // The whole pass, kernels and launchers, as templates on the element type; compiled once per
 // type, by pgmg_postpre_f64.hip (20 kernel instantiations) and pgmg_postpre_f32.hip (12): one
 // translation unit for both was by far the longest compile of the build
-// (profiles/fused_split/build_times.txt).
+// (profiles/fused_split/build_times.txt).  The sampled-check forms of the cross-cycle pass are
+// compiled by pgmg_postpre_f64s.hip (16) and pgmg_postpre_f32s.hip (8), see launch_pp_sampled.
 #pragma once
 #include <algorithm>
 #include <type_traits>
@@ -148,9 +149,6 @@ static_assert(kPPWaves * kPPStrideRC + 2 * kPPMarginRC + 4 <= kPPLdsRow &&
 // 0.675-0.687 with quad loads (2 waves of 4 do all the loading, ds_write_b128), 0.647-0.649
 // with quad stores only -- the knobs stay off; the pass's cost for fp32 is its per-lane work
 // on 2 columns, not the load width.
-#ifndef PGMG_PP_CHEAPCHK
-#define PGMG_PP_CHEAPCHK 0
-#endif
 #ifndef PGMG_F32_QLOAD
 #define PGMG_F32_QLOAD 0
 #endif
@@ -190,7 +188,16 @@ template <class T> using PPC = typename std::conditional<pp_qc<T>(), float4, V2<
 // is stored INSTEAD of x4; the next call recomputes x4 from it), 256 the recompute form
 // (the first pass of a call that took the carry: the input is the previous call's x2, whose
 // pre-smooth -- two Jacobi stages, the carry pass's own expressions, bitwise its x4 -- runs in
-// front of the correction; the pipeline's rows lag two more).
+// front of the correction; the pipeline's rows lag two more), 512 sampled checks.
+// Sampled checks (OPT & 512; speculative calls on one GPU, pgmg_spec.hip): the two checks'
+// residuals r(x1), r(x3) and their sums are compiled only for the first row of one step of the
+// loop body each -- 1 row in 6 (depth 3, none in the remainder steps) or in 4 (depth 2): the
+// band's first row and every 6th (4th) after it, so a band of any height sums a row -- with the full form's expressions and its in-band and ownership masks, into the same
+// partial slots.  A sampled partial adds a subsequence of the full partial's non-negative terms
+// in the same order, so it is a lower bound of it (rounding is monotonic): enough to prove that
+// a check cannot fire, never to decide that it does (k_postpre_decide only sees full sums).
+// Everything the pass stores is the full form's, bit for bit.  Not for R2 or OPT & 64.
+template <int K> using BodyStep = std::integral_constant<int, K>;   // (postpre_lds_run's step)
 // Logical block of the 2D grid (x: column block, y: band).
 struct Blk {
     int x, y;
@@ -270,6 +277,8 @@ __device__ __forceinline__ void postpre_lds_run(const PostPreArgsT<T> &a, const 
     constexpr bool CARRY = (OPT & 128) != 0;        // the carry pass
     constexpr int ST = pp_stride<OPT>(), MG = pp_margin<OPT>();
     constexpr int LAG = RC ? 2 : 0;                 // rows the correction lags the input
+    constexpr bool SAMPLED = (OPT & 512) != 0;      // sampled checks
+    static_assert(!SAMPLED || (!R2 && !(OPT & 64)), "sampled checks: the cross-cycle pass, one GPU");
     const int N = a.N, Nc = a.Nc;
     const long long P = a.P, Pc = a.Pc;
     const int jcb = a.jc0 + bk.y * a.rows_per_block;
@@ -413,7 +422,12 @@ __device__ __forceinline__ void postpre_lds_run(const PostPreArgsT<T> &a, const 
     // pair gi: compute from slot gi & 1; pair gi+1 (set (gi+1) & 1) -> the other slot;
     // issue pair gi+3 into the set just freed; one barrier
     T wprev = T(0);   // dpp_shl(d2.x) of the previous restriction row (d0 starts as zero)
-    auto step = [&](int gi, PV (&px)[R], PV (&pf)[R], PC &pe) {
+    // kb (compile time): the step's place in the loop body, -1 in the remainder steps.  Sampled
+    // checks: the first row of body step SPOST carries the post check and that of step SPRE the
+    // pre check -- the steps whose first row's check falls on the band's first row 2jcb (then
+    // every 2D rows), so that a band of any height sums at least that row
+    constexpr int SPOST = (4 + LAG) % D, SPRE = (5 + LAG) % D;
+    auto step = [&](auto kb, int gi, PV (&px)[R], PV (&pf)[R], PC &pe) {
         // keep the scheduler inside one pair: interleaving the unrolled pairs only raises
         // the register pressure (the loads of a pair are issued two pairs ahead anyway)
         __builtin_amdgcn_sched_barrier(0);
@@ -430,6 +444,10 @@ __device__ __forceinline__ void postpre_lds_run(const PostPreArgsT<T> &a, const 
         #pragma unroll
         for (int s = 0; s < R; ++s) {
             const int ii = i + s;
+            // (s is a constant of the unrolled body: the other rows' checks are not compiled)
+            constexpr int KB = decltype(kb)::value;
+            const bool chk1 = !SAMPLED || (KB == SPOST && s == 0);
+            const bool chk3 = !SAMPLED || (KB == SPRE && s == 0);
             const V2<T> xr = ldv(&sx[slot][s][xo + SH]);
             // f[ii]: from LDS, or (GENF) generated once here and carried in the f window
             // (regenerating it at every use instead: fewer VGPRs, 8 more multiplies per
@@ -465,12 +483,8 @@ __device__ __forceinline__ void postpre_lds_run(const PostPreArgsT<T> &a, const 
             // FAST: the neighbour sums of x1 row ii-2 and x3 row ii-4, each shared by a sweep
             // and a check
             const V2<T> sb = FAST ? nsum<T>(b0, b1, b2, nb1) : z;
-            {   // post check: r(x1) on row ii-2
-#if PGMG_PP_CHEAPCHK   // measurement only: what the checks' residuals cost (the sums are wrong)
-                const V2<T> r1 = b1;
-#else
+            if (chk1) {   // post check: r(x1) on row ii-2
                 const V2<T> r1 = FAST ? rsum<T>(sb, b1, fq2, ih) : rsn<T>(b0, b1, b2, nb1, fq2, ih);
-#endif
                 const int row = L - 2;
                 if constexpr (chk_sel<T>()) {
                     acc1 = chk_acc<T>(acc1, r1, row >= olo && row < ohi && k.own, k.by);
@@ -500,12 +514,8 @@ __device__ __forceinline__ void postpre_lds_run(const PostPreArgsT<T> &a, const 
             const V2<T> g2 = FAST ? jsum<T, EDGE>(nsum<T>(c0, c1, c2, nc1), c1, hq3, k, boundary_row(L - 3, N))
                                   : jsh<T, EDGE>(c0, c1, c2, nc1, hq3, k, boundary_row(L - 3, N));
             const V2<T> sgg = FAST ? nsum<T>(g0, g1, g2, ng1) : z;
-            {   // pre check: r(x3) on row ii-4
-#if PGMG_PP_CHEAPCHK
-                const V2<T> r3 = g1;
-#else
+            if (chk3) {   // pre check: r(x3) on row ii-4
                 const V2<T> r3 = FAST ? rsum<T>(sgg, g1, fq4, ih) : rsn<T>(g0, g1, g2, ng1, fq4, ih);
-#endif
                 const int row = L - 4;
                 if constexpr (chk_sel<T>()) {
                     acc2 = chk_acc<T>(acc2, r3, row >= olo && row < ohi && k.own, k.by);
@@ -568,16 +578,16 @@ __device__ __forceinline__ void postpre_lds_run(const PostPreArgsT<T> &a, const 
         // back in its register (a guarded step would merge two paths and force copies)
         int gi = 0;
         for (; gi + 3 <= ng; gi += 3) {
-            step(gi, pxB, pfB, peB);
-            step(gi + 1, pxC, pfC, peC);
-            step(gi + 2, pxA, pfA, peA);
+            step(BodyStep<0>{}, gi, pxB, pfB, peB);
+            step(BodyStep<1>{}, gi + 1, pxC, pfC, peC);
+            step(BodyStep<2>{}, gi + 2, pxA, pfA, peA);
         }
-        if (gi < ng) step(gi, pxB, pfB, peB);
-        if (gi + 1 < ng) step(gi + 1, pxC, pfC, peC);
+        if (gi < ng) step(BodyStep<-1>{}, gi, pxB, pfB, peB);
+        if (gi + 1 < ng) step(BodyStep<-1>{}, gi + 1, pxC, pfC, peC);
     } else {
         for (int gi = 0; gi < ng; gi += 2) {
-            step(gi, pxB, pfB, peB);
-            if (gi + 1 < ng) step(gi + 1, pxA, pfA, peA);
+            step(BodyStep<0>{}, gi, pxB, pfB, peB);
+            if (gi + 1 < ng) step(BodyStep<1>{}, gi + 1, pxA, pfA, peA);
         }
     }
     const int slot = bk.y * gridDim.x + bk.x;
@@ -645,6 +655,40 @@ static void launch_pp_form(const PostPreArgsT<T> &a, bool genf, dim3 g, dim3 b, 
     else launch_pp_form<T, false, OPT>(a, g, b, s);
 }
 
+// The sampled-check forms (OPT | 512) of every form above: `form` is the full-sum switch's
+// value (16 FAST, 128 carry, 256 recompute).  Instantiated by translation units of their own
+// (pgmg_postpre_f64s.hip, pgmg_postpre_f32s.hip: these are the build's longest compiles), which
+// define PGMG_POSTPRE_SAMPLED_TU; the others only see the declaration.
+template <class T>
+void launch_pp_sampled(const PostPreArgsT<T> &a, int form, bool genf, dim3 g, dim3 b, hipStream_t s);
+#ifdef PGMG_POSTPRE_SAMPLED_TU
+template <class T>
+void launch_pp_sampled(const PostPreArgsT<T> &a, int form, bool genf, dim3 g, dim3 b, hipStream_t s)
+{
+    if constexpr (sizeof(T) == 8) {
+        switch (form) {
+        case 0: launch_pp_form<T, 2 | 512>(a, genf, g, b, s); break;
+        case 16: launch_pp_form<T, 2 | 16 | 512>(a, genf, g, b, s); break;
+        case 128: launch_pp_form<T, 2 | 128 | 512>(a, genf, g, b, s); break;
+        case 144: launch_pp_form<T, 2 | 16 | 128 | 512>(a, genf, g, b, s); break;
+        case 256: launch_pp_form<T, 2 | 256 | 512>(a, genf, g, b, s); break;
+        case 272: launch_pp_form<T, 2 | 16 | 256 | 512>(a, genf, g, b, s); break;
+        case 384: launch_pp_form<T, 2 | 128 | 256 | 512>(a, genf, g, b, s); break;
+        default: launch_pp_form<T, 2 | 16 | 128 | 256 | 512>(a, genf, g, b, s); break;
+        }
+    } else {
+        switch (form) {
+        case 0: launch_pp_form<T, 2 | 512>(a, genf, g, b, s); break;
+        case 128: launch_pp_form<T, 2 | 128 | 512>(a, genf, g, b, s); break;
+        case 256: launch_pp_form<T, 2 | 256 | 512>(a, genf, g, b, s); break;
+        default: launch_pp_form<T, 2 | 128 | 256 | 512>(a, genf, g, b, s); break;
+        }
+    }
+}
+#define PGMG_POSTPRE_SAMPLED_INSTANTIATE(T) \
+    template void launch_pp_sampled<T>(const PostPreArgsT<T> &, int, bool, dim3, dim3, hipStream_t);
+#endif
+
 template <class T>
 int launch_postpre(const PostPreArgsT<T> &a0, hipStream_t s)
 {
@@ -661,9 +705,12 @@ int launch_postpre(const PostPreArgsT<T> &a0, hipStream_t s)
     const dim3 g(gx, gy), b(t);
     const bool genf = a.gfx != nullptr;
     const bool fast = a.fast && sizeof(T) == 8;   // FAST mode: fp64
+    if (a.sampled && a.partials3 != nullptr) return PGMG_ERR_ARG;        // one GPU only
     if (a.partials3 != nullptr) {
         if (genf) launchk(k_postpre_lds<T, true, true, 2>, g, b, s, a);
         else launchk(k_postpre_lds<T, true, false, 2>, g, b, s, a);
+    } else if (a.sampled) {
+        launch_pp_sampled<T>(a, ((fast ? 16 : 0) | (carry ? 128 : 0) | (rc ? 256 : 0)), genf, g, b, s);
     } else if constexpr (sizeof(T) == 8) {
         switch ((fast ? 16 : 0) | (carry ? 128 : 0) | (rc ? 256 : 0)) {
         case 0: launch_pp_form<T, 2>(a, genf, g, b, s); break;

@@ -34,6 +34,24 @@ using namespace pgmg;
 // again with in-stream decisions, and the context stops speculating (a fired check means
 // the solver is near convergence, where checks keep firing).  Results and statistics
 // are therefore always the exact path's.  The call ends with one host synchronisation.
+//
+// Sampled checks (one GPU).  The finest level's cross-cycle pass spends a quarter of its
+// arithmetic on the residuals of its two checks, whose only use on a speculative call is this
+// proof that they cannot fire.  A sum over a subset of the rows proves it as well, by the
+// strips' argument: the sampled partial adds a subsequence of the full partial's non-negative
+// terms in the same order, every later reduction is the same tree over inputs that are no
+// larger, and rounding and sqrt are monotonic -- so sqrt(sampled sum) <= sqrt(full sum), and
+// could_fire = sqrt(s) < eps (1 + 1e-12) on the sampled sum stays a superset of "the full sum
+// fires" (a NaN term in an unsampled row makes the full sum NaN, which does not fire either).
+// Such a check is logged as a lower bound (CheckRef::bound) and may only be recorded "does not
+// fire"; must_fire proves nothing from a bound.  A sampled check that could fire rolls the
+// segment back as any other; the rerun launches the full-sum form and decides in-stream.  If a
+// cross-cycle check then fires, the context stops speculating as before; if none does, the
+// finest norm sits between eps and about sqrt(6) eps (1 row in 6 sampled): the context keeps
+// speculating with full-sum finest passes (SpecHistory::full_sums) until the next problem or
+// eps.  The level-0 norms of the reply (hnorm, lvl_hist[0]) are lower bounds then; nothing
+// predicts from them (spec_mark_levels, spec_level_trend's callers and spec_plan_segment all
+// start at level 1).  PGMG_FLAG_FULL_CHECKS launches the full-sum form everywhere.
 // ---------------------------------------------------------------------------
 
 namespace pgmg {
@@ -55,10 +73,12 @@ __global__ __launch_bounds__(256) void k_verify_checks(const CheckRef *checks, d
         // flag = the prediction may be wrong: "does not fire" checks that could fire, "fires"
         // checks that could not (same margin the other way); in-stream checks are logged
         // for the norms only
+        // a lower bound (c.bound, sampled checks): could_fire is a superset of "the full sum
+        // fires" all the same; must_fire would prove nothing, so any other record is flagged
         const bool could_fire = sqrt(s) < eps * (1.0 + 1e-12);
         const bool must_fire = sqrt(s) < eps * (1.0 - 1e-12);
         out[blockIdx.x] = c.expect == 0 ? (could_fire ? 1u : 0u)
-                                        : (c.expect == 1 ? (must_fire ? 0u : 1u) : 0u);
+                                        : (c.bound ? 1u : (c.expect == 1 ? (must_fire ? 0u : 1u) : 0u));
         norm[blockIdx.x] = sqrt(s);
     }
 }
@@ -387,6 +407,8 @@ static int spec_plan_segment(pgmg_ctx *c, int seg)
     return best_k;
 }
 
+// (a level-0 norm of a sampled check -- hnorm[i] with chks[i].bound -- is a lower bound of the
+// check's norm; lvl_hist[0] is kept for traces only: every reader below starts at level 1)
 static void spec_record_norms(pgmg_ctx *c, int n)
 {
     for (int i = 0; i < n; ++i) {
@@ -576,11 +598,15 @@ int pgmg::run_cycles_spec(pgmg_ctx *c, int ncycles, int gamma)
                 c->hist.wmin.clear();
                 c->hist.wrho.clear();
             }
+            // a flagged finest-level check that is a lower bound (sampled) proves nothing yet:
+            // the rerun's full sums decide below whether the context stops speculating
+            bool bound_hit = false;
             for (int i = 0; i < n; ++i)
                 if (c->hflag[i] || overflow) {
                     const int l = c->chks[i].level;
                     if (l == 0) {
-                        c->hist.spec_off = true;
+                        if (c->chks[i].bound && !overflow) bound_hit = true;
+                        else c->hist.spec_off = true;
                     } else {
                         c->hist.lvl_exact[l] = 1;
                         if (c->chks[i].expect == 1) {   // a "fires" prediction failed
@@ -598,7 +624,23 @@ int pgmg::run_cycles_spec(pgmg_ctx *c, int ncycles, int gamma)
             HIPC(hipMemcpyAsync(c->stats, c->stats_bk, 4 * sizeof(unsigned long long),
                                 hipMemcpyDeviceToDevice, c->s));
             c->call.x_in = seg_first ? ext_in : nullptr;
-            return run_cycles_plain(c, ncycles, gamma, false);
+            if (!bound_hit || c->hist.spec_off) return run_cycles_plain(c, ncycles, gamma, false);
+            // Only sampled checks could fire.  stats[2] / stats[3] count the cross-cycle checks
+            // that k_postpre_decide let fire (nothing else writes them; the opening k_pre's and
+            // the closing k_post's checks were logged as full sums and did not fire): unchanged
+            // over the rerun, the finest norm is above eps but within the sample's factor of it.
+            if ((e = run_cycles_plain(c, ncycles, gamma, false))) return e;
+            PGMG_TRY(stream_wait(c));
+            unsigned long long now[2] = {0, 0}, was[2] = {0, 0};
+            HIPC(hipMemcpy(now, c->stats + 2, sizeof(now), hipMemcpyDeviceToHost));
+            HIPC(hipMemcpy(was, c->stats_bk + 2, sizeof(was), hipMemcpyDeviceToHost));
+            if (now[0] == was[0] && now[1] == was[1]) {
+                c->hist.full_sums = true;
+                ++c->sampled_n[1];
+            } else {
+                c->hist.spec_off = true;
+            }
+            return PGMG_OK;
         }
         if (seg_first && c->call.carry_took) ++c->carry_n[0];
         if (made) {
@@ -628,6 +670,15 @@ int pgmg_carry_info(pgmg_ctx *c, long long out[3])
 {
     if (!c || !out) return set_err(PGMG_ERR_ARG, "null argument");
     for (int i = 0; i < 3; ++i) out[i] = c->carry_n[i];
+    return PGMG_OK;
+}
+
+int pgmg_spec_sampled_info(pgmg_ctx *c, long long out[3])
+{
+    if (!c || !out) return set_err(PGMG_ERR_ARG, "null argument");
+    out[0] = c->sampled_n[0];
+    out[1] = c->sampled_n[1];
+    out[2] = c->hist.full_sums ? 1 : 0;
     return PGMG_OK;
 }
 
