@@ -311,6 +311,11 @@ int pgmg_sync(pgmg_ctx *ctx);
 /* Download phi (N*N, reference layout).  world > 1: every rank receives the
  * full grid (strips are gathered to all ranks). */
 int pgmg_get_solution(pgmg_ctx *ctx, double *phi_host);
+/* Download the level-0 right-hand side as the context stores it (N*N, reference layout, an fp32
+ * context's values widened): the f given to pgmg_set_problem, the analytic RHS it generated for
+ * f = NULL, the last staged copy of a device-bound problem's f, or the divergence pgmg_project
+ * wrote.  One GPU (world 1), after pgmg_set_problem*; only reads the problem. */
+int pgmg_get_rhs(pgmg_ctx *ctx, double *f_host);
 /* The same with the strips gathered to rank `root` only (collective: every rank calls it;
  * ranks other than root may pass phi_host = NULL).  root < 0: every rank, as above. */
 int pgmg_gather_solution(pgmg_ctx *ctx, int root, double *phi_host);
@@ -684,6 +689,70 @@ int pgmg_solve_extrap(pgmg_ctx *ctx, const pgmg_solve_opts *o, int nu, double om
 int pgmg_gradient(pgmg_ctx *ctx, int order, double scale, double *d_gx, double *d_gy, double *norm);
 int pgmg_gradient_time(pgmg_ctx *ctx, int order, int reps, double *ms_per_pass, double *bytes);
 
+/* ---- Projection ----------------------------------------------------------------------------
+ * pgmg_project(ctx, opts, order, nu, omega, d_u, d_v, measure_after, info): the divergence-free
+ * part of a velocity field (u*, v*) on the device, in place, without a host round trip:
+ *     f = -div(u*, v*),   -lap(phi) = f with phi's frame as Dirichlet data (the problem every
+ *     solve of the library solves),   (u, v) = (u*, v*) - grad(phi).
+ * d_u and d_v are the caller's N x N device arrays of doubles at pitch N, element (j, i) at x =
+ * i h, y = j h; h is the context's finest mesh width.  fp64, one GPU.  Synchronous.  The
+ * expressions follow "Gradient of the solution" above: evaluated left to right as written, one
+ * rounding per operation, no fused multiply-add; "the line formulas" are that section's g[k] of
+ * order 2 and 4, one-sided points included, and w its factor (scale * 0.5 / h, or
+ * scale / (12.0 * h)).
+ *   The divergence, on all N x N points, frame included:
+ *     dx(y, x) = the line formula along x on row y of u, times w
+ *     dy(y, x) = the line formula along y on column x of v, times w
+ *     out(y, x) = dx + dy            each of dx and dy rounded after its * w, then one add
+ *   The update, on all N x N points, frame included:
+ *     u(y, x) <- u(y, x) + gx(y, x),  v(y, x) <- v(y, x) + gy(y, x)
+ *   gx, gy exactly pgmg_gradient's values for that phi, h, order and scale: one more rounding
+ *   per component.  Each point reads and writes only its own u and v.
+ * The steps:
+ *   1. The stored level-0 right-hand side becomes the divergence of (u, v) at scale = -1.0,
+ *      written by the pass straight into the context's f grid; info->div_before = sqrt(sum f^2)
+ *      over all points from that pass's own sums (pgmg_gradient's scheme and decomposition).  The
+ *      context's problem is then one with a caller's f: nothing is regenerated, PGMG_MON_ERROR is
+ *      refused, the statistics and the speculation history start over and the carry is dropped --
+ *      in every observable the state pgmg_set_problem(the current phi, that f downloaded)
+ *      leaves.  phi is not touched: its frame is the Dirichlet data, its interior is ignored.
+ *   2. order 2: pgmg_fmg_bc(ctx, nu, omega), then pgmg_solve_damped(ctx, opts, omega,
+ *      &info->solve.fine).  order 4: pgmg_solve_extrap(ctx, opts, nu, omega, &info->solve).
+ *   3. The update with phi where it lies, at scale = -1.0.
+ *   4. measure_after != 0: info->div_after = the norm of step 1 on the corrected field, from a
+ *      pass that stores nothing.
+ * Afterwards phi is the potential, its frame bit for bit the one it had, and f stays the
+ * divergence; a later pgmg_vcycle or pgmg_gradient continues from there.  The projection is
+ * approximate: the div . grad of these stencils is not the 5-point Laplacian.  On (u*, v*) = w +
+ * grad(psi), psi = sin(pi x) sin(pi y), w the divergence-free field of tests/test_proj_cpu.py,
+ * solved with nu = 2, omega = 0.5, eps < 0, atol = 1e-10 ||f||, the relative error of (u, v)
+ * against w falls from 2.1e-3 (N = 33) to 3.2e-5 (N = 257) at order 2, by 4 per doubling, and from
+ * 9.0e-6 to 1.6e-9 at order 4, by 17 per doubling; ||div(u)|| / ||div(u*)|| is 8.6e-4 and 1.1e-7
+ * at N = 257.  The model is tests/proj_model.py.
+ * Errors, all before f or anything else is written.  PGMG_ERR_ARG: a null argument; invalid opts
+ * (pgmg_solve's rule); an order other than 2 or 4; nu < 1; omega not finite, <= 0 or > 1 (the
+ * undamped route stalls on a general f); u or v not device memory; u and v overlapping each other
+ * or the context's grids; a coarsest level with fewer than 5 points per side; at order 4, N < 9
+ * or a half-resolution grid whose coarsest level has fewer than 5.  PGMG_ERR_STATE: before
+ * pgmg_set_problem; world > 1; an fp32 context; a device-bound problem (pgmg_set_problem_device:
+ * its f is the caller's const array); PGMG_MON_ERROR in opts.
+ * pgmg_project_time: `reps` passes back to back between two hipEvents, after two warm ones, on
+ * three context-owned scratch arrays allocated on the first call (24 N^2 bytes): which = 0 the
+ * divergence with out and norm (both launches), which = 1 the update of both components; mean
+ * device ms per pass and its algorithmic bytes, 24 N^2 and 40 N^2.  Neither phi nor f is
+ * written.  fp64, one GPU, after pgmg_set_problem*. */
+typedef struct pgmg_project_info {
+    pgmg_extrap_info solve;      /* order 4: as pgmg_solve_extrap fills it; order 2: .fine is the
+                                    damped solve, every other field 0 */
+    double div_before;           /* sqrt(sum f^2) over all points, from step 1's own pass */
+    double div_after;            /* the same of the corrected field; NaN unless measure_after */
+    double div_ms, update_ms;    /* device time of steps 1 and 3 */
+    double elapsed_ms;           /* host wall time of the call */
+} pgmg_project_info;
+int pgmg_project(pgmg_ctx *ctx, const pgmg_solve_opts *o, int order, int nu, double omega,
+                 double *d_u, double *d_v, int measure_after, pgmg_project_info *info);
+int pgmg_project_time(pgmg_ctx *ctx, int which, int order, int reps, double *ms, double *bytes);
+
 /* Cumulative smoother sweeps and early exits since set_problem.  The sweeps are the
  * oracle's.  The early exits are those that cut a smoother call short: the check after a
  * call's last sweep cannot change the result and is not evaluated, so where the oracle's
@@ -849,6 +918,25 @@ int pgmg_extrap_grid(double *d_fine, const double *d_coarse, int Nf, void *strea
  * nothing enqueued. */
 int pgmg_gradient_grid(const double *d_phi, double *d_gx, double *d_gy, int N, double h, int order,
                        double scale, double *norm, void *stream);
+/* The divergence of pgmg_project ("Projection" above) on caller-owned device arrays, fp64:
+ * out = dx(u) + dy(v) on all N x N points, d_u, d_v and d_out at pitch N, u and v only read.
+ * d_out may be NULL when norm is not: the pass then stores nothing, reads 16 B per point and only
+ * sums.  norm receives sqrt(sum out^2) over all points, by pgmg_gradient's scheme on its
+ * decomposition (a function of N alone); the partial sums belong to the per-stream set below.
+ * norm == NULL: asynchronous on `stream`; otherwise synchronous.  N not 2^k + 1 with k >= 2, h of
+ * 0 or not finite (negative is legal), an order other than 2 or 4, a non-finite scale, a null u
+ * or v, both out and norm NULL, an out that is not device memory or that overlaps u or v:
+ * PGMG_ERR_ARG, nothing enqueued. */
+int pgmg_divergence_grid(const double *d_u, const double *d_v, double *d_out, int N, double h,
+                         int order, double scale, double *norm, void *stream);
+/* The update of pgmg_project on caller-owned device arrays, fp64: u <- u + gx, v <- v + gy on all
+ * N x N points, gx and gy exactly pgmg_gradient_grid's values for that phi, h, order and scale.
+ * d_u and d_v at pitch N, either may be NULL (both: PGMG_ERR_ARG); d_phi at pitch_phi >= N, only
+ * read.  Each point reads and writes only its own u and v: safe in place.  Asynchronous on
+ * `stream`.  The other argument rules are pgmg_gradient_grid's; u, v and phi must not overlap one
+ * another. */
+int pgmg_gradient_add_grid(const double *d_phi, long long pitch_phi, double *d_u, double *d_v,
+                           int N, double h, int order, double scale, void *stream);
 /* The op-level entries keep one scratch set (partial sums, flags, ping-pong buffer) per
  * stream they were called on; this waits for `stream` and frees its set (a later op on the
  * same stream allocates a fresh one).  Call it before destroying a stream the ops used. */

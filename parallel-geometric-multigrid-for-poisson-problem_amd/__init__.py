@@ -28,7 +28,7 @@ from ._capi import (PGMG_FLAG_LOOPBACK, PGMG_FLAG_NO_CROSS, PGMG_FLAG_NO_GRAPH,
                     PGMG_MON_RESIDUAL, PGMG_MON_ERROR, PGMG_CYCLE_V, PGMG_CYCLE_W, PGMG_CYCLE_F,
                     PGMG_STOP_CONVERGED, PGMG_STOP_MAX_CYCLES, PGMG_STOP_STALLED,
                     PGMG_STOP_NONFINITE, PgmgMonitorOut, PgmgSolveOpts, PgmgSolveInfo,
-                    PgmgExtrapInfo, check, load)
+                    PgmgExtrapInfo, PgmgProjectInfo, check, load)
 
 PKG_DIR = pathlib.Path(__file__).resolve().parent
 
@@ -43,6 +43,7 @@ __all__ = [
     "PGMG_MON_RESIDUAL", "PGMG_MON_ERROR", "PGMG_CYCLE_V", "PGMG_CYCLE_W", "PGMG_CYCLE_F",
     "PGMG_STOP_CONVERGED", "PGMG_STOP_MAX_CYCLES", "PGMG_STOP_STALLED", "PGMG_STOP_NONFINITE",
     "PgmgSolveOpts", "PgmgSolveInfo", "PgmgMonitorOut", "PgmgExtrapInfo",
+    "PgmgProjectInfo",
 ]
 
 
@@ -276,6 +277,12 @@ class Solver:
               "pgmg_get_solution")
         return out
 
+    def rhs(self):
+        """The level-0 right-hand side as the context stores it (pgmg_get_rhs)."""
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        check(self.lib.pgmg_get_rhs(self.h, out.ctypes.data_as(C.c_void_p)), "pgmg_get_rhs")
+        return out
+
     def solution_hash(self, root=0):
         """FNV-64 of phi (hex string, the golden fixtures' format) on rank `root`; collective
         on row strips (other ranks get None)."""
@@ -425,6 +432,43 @@ class Solver:
         ms, b = C.c_double(), C.c_double()
         check(self.lib.pgmg_gradient_time(self.h, int(order), int(reps), C.byref(ms), C.byref(b)),
               "pgmg_gradient_time")
+        return ms.value, b.value
+
+    def project(self, u, v, order=4, nu=2, damp=0.5, rtol=0.0, atol=0.0, max_cycles=30,
+                check_every=1, measure_after=False):
+        """Make the velocity field (u, v) divergence free in place (pgmg_project): the level-0
+        right-hand side becomes f = -div(u, v), formed on the device; the problem with the frame
+        of the current phi as Dirichlet data is solved from fmg(nu, damp, "keep") by the damped
+        solve (order 2) or by solve(order=4)'s extrapolated pair (order 4); then u -= phi_x,
+        v -= phi_y with the stencils of that order.  u, v: contiguous N x N float64 CUDA tensors,
+        element (j, i) at x = i h, y = j h.  State the target as atol (~1e-10 ||f||) and create
+        the Solver with eps < 0, as for solve(order=4).  Returns the PgmgProjectInfo with
+        `.history` (the fine solve's checks); `.div_before` is ||f||, `.div_after` the same of the
+        corrected field with measure_after=True (NaN otherwise).  Afterwards phi is the potential
+        and f the divergence.  fp64, one GPU, context-owned problems."""
+        import torch
+        N = self.N
+        for t in (u, v):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64
+                    and tuple(t.shape) == (N, N) and t.is_contiguous()):
+                raise ValueError("u and v must be contiguous N x N float64 CUDA tensors")
+        o = PgmgSolveOpts()
+        check(self.lib.pgmg_solve_opts_default(C.byref(o)), "pgmg_solve_opts_default")
+        o.rtol, o.atol, o.max_cycles, o.check_every = rtol, atol, int(max_cycles), int(check_every)
+        info = PgmgProjectInfo()
+        check(self.lib.pgmg_project(self.h, C.byref(o), int(order), int(nu), float(damp), _dptr(u),
+                                    _dptr(v), int(bool(measure_after)), C.byref(info)),
+              "pgmg_project")
+        info.history = self.history()
+        return info
+
+    def project_time(self, which, order=4, reps=20):
+        """(mean device ms, algorithmic bytes) of one pass of project over `reps` back to back on
+        context-owned arrays (pgmg_project_time; measurement): which=0 the divergence with its
+        output and norm, which=1 the update of both components.  Leaves phi and f alone."""
+        ms, b = C.c_double(), C.c_double()
+        check(self.lib.pgmg_project_time(self.h, int(which), int(order), int(reps), C.byref(ms),
+                                         C.byref(b)), "pgmg_project_time")
         return ms.value, b.value
 
     def history(self):
@@ -706,6 +750,36 @@ class _Ops:
                                         int(order), float(scale), C.byref(out) if norm else None,
                                         stream), "pgmg_gradient_grid")
         return (gx, gy, out.value) if norm else (gx, gy)
+
+    def divergence(self, u, v, h, out=None, order=4, scale=1.0, stream=None, norm=False):
+        """out = scale * (du/dx + dv/dy) on N x N float64 device arrays (pgmg_divergence_grid;
+        N = 2^k + 1, k >= 2; h finite and not 0), by the line differences of ops.gradient.
+        norm=False: returns out (allocated when None), asynchronous on `stream`.  norm=True:
+        returns (out, sqrt(sum out^2)), synchronous; with out=None nothing is stored and out is
+        returned as None."""
+        import torch
+        N = u.shape[0]
+        assert tuple(u.shape) == (N, N) and tuple(v.shape) == (N, N), (u.shape, v.shape)
+        if out is None and not norm:
+            out = torch.empty_like(u)
+        assert out is None or tuple(out.shape) == (N, N), out.shape
+        n = C.c_double()
+        check(load().pgmg_divergence_grid(self._ptr(u), self._ptr(v), self._ptr(out), N, float(h),
+                                          int(order), float(scale), C.byref(n) if norm else None,
+                                          stream), "pgmg_divergence_grid")
+        return (out, n.value) if norm else out
+
+    def gradient_add(self, phi, h, u=None, v=None, order=4, scale=1.0, stream=None):
+        """u += scale * phi_x, v += scale * phi_y in place on N x N float64 device arrays
+        (pgmg_gradient_add_grid), the added values exactly ops.gradient's; either of u, v may be
+        None.  Asynchronous on `stream`."""
+        N = phi.shape[0]
+        assert tuple(phi.shape) == (N, N), phi.shape
+        for t in (u, v):
+            assert t is None or tuple(t.shape) == (N, N), t.shape
+        check(load().pgmg_gradient_add_grid(self._ptr(phi), N, self._ptr(u), self._ptr(v), N,
+                                            float(h), int(order), float(scale), stream),
+              "pgmg_gradient_add_grid")
 
     def release(self, stream=None):
         """Wait for `stream` and free the scratch set the ops keep for it (pgmg_ops_release)."""

@@ -121,6 +121,11 @@ class PgmgExtrapInfo(C.Structure):
                 ("extrap_ms", C.c_double), ("elapsed_ms", C.c_double)]
 
 
+class PgmgProjectInfo(C.Structure):
+    _fields_ = [("solve", PgmgExtrapInfo), ("div_before", C.c_double), ("div_after", C.c_double),
+                ("div_ms", C.c_double), ("update_ms", C.c_double), ("elapsed_ms", C.c_double)]
+
+
 # (name, restype, argtypes) for every symbol include/pgmg.h declares
 _P = C.c_void_p
 _DP = C.POINTER(C.c_double)
@@ -140,6 +145,7 @@ SIGNATURES = [
     ("pgmg_fcycle", C.c_int, [_P, C.c_int]),
     ("pgmg_sync", C.c_int, [_P]),
     ("pgmg_get_solution", C.c_int, [_P, _P]),
+    ("pgmg_get_rhs", C.c_int, [_P, _P]),
     ("pgmg_gather_solution", C.c_int, [_P, C.c_int, _P]),
     ("pgmg_solution_hash", C.c_int, [_P, C.c_int, C.POINTER(C.c_ulonglong)]),
     ("pgmg_residual_norm", C.c_int, [_P, _DP]),
@@ -160,6 +166,9 @@ SIGNATURES = [
                                     C.POINTER(PgmgExtrapInfo)]),
     ("pgmg_gradient", C.c_int, [_P, C.c_int, C.c_double, _P, _P, _DP]),
     ("pgmg_gradient_time", C.c_int, [_P, C.c_int, C.c_int, _DP, _DP]),
+    ("pgmg_project", C.c_int, [_P, C.POINTER(PgmgSolveOpts), C.c_int, C.c_int, C.c_double, _P, _P,
+                               C.c_int, C.POINTER(PgmgProjectInfo)]),
+    ("pgmg_project_time", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _DP, _DP]),
     ("pgmg_stats", C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     ("pgmg_stats_detail", C.c_int, [_P, C.POINTER(C.c_longlong)]),
     ("pgmg_last_elapsed_ms", C.c_int, [_P, _DP]),
@@ -198,6 +207,10 @@ SIGNATURES = [
     ("pgmg_extrap_grid", C.c_int, [_P, _P, C.c_int, _P]),
     ("pgmg_gradient_grid", C.c_int, [_P, _P, _P, C.c_int, C.c_double, C.c_int, C.c_double, _DP,
                                      _P]),
+    ("pgmg_divergence_grid", C.c_int, [_P, _P, _P, C.c_int, C.c_double, C.c_int, C.c_double, _DP,
+                                       _P]),
+    ("pgmg_gradient_add_grid", C.c_int, [_P, C.c_longlong, _P, _P, C.c_int, C.c_double, C.c_int,
+                                         C.c_double, _P]),
     ("pgmg_ops_release", C.c_int, [_P]),
     ("pgmg_device_alloc", C.c_int, [C.POINTER(_P), C.c_size_t]),
     ("pgmg_device_free", C.c_int, [_P]),

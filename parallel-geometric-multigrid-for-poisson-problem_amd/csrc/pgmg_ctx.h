@@ -269,6 +269,11 @@ struct pgmg_ctx {
     double *grad_buf = nullptr;
     int grad_cap = 0;             // workgroups grad_buf holds partials for
     double *grad_out = nullptr;
+    // pgmg_project (pgmg_project.hip): the events around its divergence and update passes, and
+    // pgmg_project_time's three scratch arrays (N * N doubles each, a registered allocation), all
+    // made on the first call that needs them
+    hipEvent_t pj_ev0 = nullptr, pj_ev1 = nullptr;
+    double *pj_out = nullptr;
 };
 
 namespace pgmg {

@@ -143,6 +143,12 @@ int pgmg_destroy(pgmg_ctx *c)
         unregister_alloc(c->grad_out);
         (void)hipFree(c->grad_out);
     }
+    if (c->pj_out) {
+        unregister_alloc(c->pj_out);
+        (void)hipFree(c->pj_out);
+    }
+    if (c->pj_ev0) (void)hipEventDestroy(c->pj_ev0);
+    if (c->pj_ev1) (void)hipEventDestroy(c->pj_ev1);
     if (c->ex_ev0) (void)hipEventDestroy(c->ex_ev0);
     if (c->ex_ev1) (void)hipEventDestroy(c->ex_ev1);
     if (c->fmg_tab) (void)hipFree(c->fmg_tab);
@@ -421,6 +427,18 @@ static int problem_reset(pgmg_ctx *c)
     return PGMG_OK;
 }
 
+// A captured cycle (pgmg_cycle.hip, run_cycles_plain) holds the tables its level-0 passes
+// regenerate f from, or none, in its kernel arguments: after a change between an analytic f and a
+// stored one (old: c->rgfx of before the change) it is captured again
+static int drop_graph_of_other_rhs(pgmg_ctx *c, const double *old)
+{
+    if (c->gexec && c->rgfx != old) {
+        HIPC(hipGraphExecDestroy(c->gexec));
+        c->gexec = nullptr;
+    }
+    return PGMG_OK;
+}
+
 // level-0 right-hand side rows [r0, r1): the host array f, or (f = NULL) the analytic RHS of
 // compute_rhs, stored and, unless PGMG_FLAG_STORED_RHS, regenerated by the level-0 passes
 static int setup_rhs(pgmg_ctx *c, const double *f, int r0, int r1)
@@ -516,7 +534,9 @@ int pgmg_set_problem(pgmg_ctx *c, const double *phi0, const double *f)
     // the cross-cycle rare-path scratch S mirrors phi's boundary too (its passes never
     // write boundary rows/columns, the k_pre that reads it passes them through)
     if (c->S.base) PGMG_TRY(mirror(c->S));
+    const double *const old = c->rgfx;
     if ((e = setup_rhs(c, f, r0, r1))) return e;
+    PGMG_TRY(drop_graph_of_other_rhs(c, old));
     return problem_reset(c);
 }
 
@@ -530,6 +550,7 @@ int pgmg_set_problem_device(pgmg_ctx *c, double *phi, const double *f)
     const int N = L.N;
     PGMG_TRY(stream_wait(c));
     int e;
+    const double *const old = c->rgfx;
     if (!f) {
         if ((e = setup_rhs(c, nullptr, 0, N))) return e;
     } else {
@@ -537,6 +558,7 @@ int pgmg_set_problem_device(pgmg_ctx *c, double *phi, const double *f)
         c->rgfx = c->rgsy = nullptr;
         c->analytic = false;
     }
+    PGMG_TRY(drop_graph_of_other_rhs(c, old));
     // in place: a cross-fused fp64 context and phi inside an allocation that covers the rows
     // and columns the finest passes read past the grid (pgmg_alloc_grid's guard)
     const intptr_t o = (intptr_t)phi;
@@ -589,6 +611,31 @@ int pgmg::set_problem_injected(pgmg_ctx *c, const double *phi_src, long long Pph
     c->gen_rhs = false;
     c->rgfx = c->rgsy = nullptr;
     c->analytic = false;
+    return problem_reset(c);
+}
+
+// A problem whose right-hand side was written on the device (pgmg_project): the level-0 f grid of
+// the fp64, one-GPU context c already holds the new f and phi stays where it lies.  What
+// pgmg_set_problem(the current phi, that f) does besides the uploads: phi mirrored into B and S,
+// a problem with a caller's f (nothing regenerated, no analytic solution), the statistics and
+// the speculation history reset, the carry dropped.  Returns with the device idle.
+int pgmg::set_problem_rhs_on_device(pgmg_ctx *c)
+{
+    if (c->fp32 || c->comm || c->ext_phi)
+        return set_err(PGMG_ERR_STATE, "device right-hand side: fp64, one GPU, context-owned only");
+    Level &L = c->lv[0];
+    const size_t bytes = (size_t)L.P * L.es * (size_t)L.N;
+    for (const Grid *g : {&L.B, &c->S})
+        if (g->base)
+            HIPC(hipMemcpyAsync(row_ptr(*g, 0, L.P, L.es), row_ptr(L.A, 0, L.P, L.es), bytes,
+                                hipMemcpyDeviceToDevice, c->s));
+    PGMG_TRY(stream_wait(c));
+    const double *const old = c->rgfx;
+    c->ext_f = nullptr;
+    c->gen_rhs = false;
+    c->rgfx = c->rgsy = nullptr;
+    c->analytic = false;
+    PGMG_TRY(drop_graph_of_other_rhs(c, old));
     return problem_reset(c);
 }
 
@@ -789,6 +836,16 @@ int pgmg_last_elapsed_ms(pgmg_ctx *c, double *ms)
 int pgmg_get_solution(pgmg_ctx *c, double *phi)
 {
     return pgmg_gather_solution(c, -1, phi);
+}
+
+int pgmg_get_rhs(pgmg_ctx *c, double *f)
+{
+    if (!c || !f) return set_err(PGMG_ERR_ARG, "null argument");
+    if (!c->have_problem) return set_err(PGMG_ERR_STATE, "pgmg_set_problem first");
+    if (c->cfg.world > 1) return set_err(PGMG_ERR_STATE, "pgmg_get_rhs: one GPU only (world 1)");
+    PGMG_TRY(stream_wait(c));
+    const Level &L = c->lv[0];
+    return download_grid(c, L.F.o, L.P, L.N, f);
 }
 
 int pgmg_gather_solution(pgmg_ctx *c, int root, double *phi)

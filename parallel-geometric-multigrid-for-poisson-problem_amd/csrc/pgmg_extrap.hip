@@ -211,7 +211,7 @@ void launch_extrap(double *fine, long long Pf, const double *coarse, long long P
     k_extrap_add<<<dim3(gx, gy), dim3(kBlock), 0, s>>>(a);
 }
 
-static int coarsest_n(int N, int n_coarse)
+int coarsest_n(int N, int n_coarse)
 {
     while (N > n_coarse) N = (N - 1) / 2 + 1;
     return N;

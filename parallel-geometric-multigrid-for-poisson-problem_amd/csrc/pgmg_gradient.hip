@@ -22,13 +22,12 @@
 #include <cmath>
 #include <string>
 
+#include "pgmg_grad_dev.h"
 #include "pgmg_host.h"
 
 using namespace pgmg;
 
 namespace pgmg {
-
-constexpr int kGradU = 4;   // rows of loads in flight per wave
 
 template <class SX>
 struct GradArgs {
@@ -41,34 +40,7 @@ struct GradArgs {
     int band;            // rows per workgroup
 };
 
-// The one-sided differences along a line, their points in ascending order, before the factor w:
-// order 2 at the first and the last point of three ...
-template <class T> __device__ __forceinline__ T os2_first(T v0, T v1, T v2)
-{
-    return T(4) * v1 - T(3) * v0 - v2;
-}
-template <class T> __device__ __forceinline__ T os2_last(T u0, T u1, T u2)
-{
-    return T(3) * u2 - T(4) * u1 + u0;
-}
-// ... order 4 at the first, second, last but one and last point of five
-template <class T> __device__ __forceinline__ T os4_first(T v0, T v1, T v2, T v3, T v4)
-{
-    return T(48) * v1 - T(25) * v0 - T(36) * v2 + T(16) * v3 - T(3) * v4;
-}
-template <class T> __device__ __forceinline__ T os4_second(T v0, T v1, T v2, T v3, T v4)
-{
-    return T(18) * v2 - T(10) * v1 - T(3) * v0 - T(6) * v3 + v4;
-}
-template <class T> __device__ __forceinline__ T os4_penult(T u0, T u1, T u2, T u3, T u4)
-{
-    return T(10) * u3 - T(18) * u2 + T(3) * u4 + T(6) * u1 - u0;
-}
-template <class T> __device__ __forceinline__ T os4_last(T u0, T u1, T u2, T u3, T u4)
-{
-    return T(25) * u4 - T(48) * u3 + T(36) * u2 - T(16) * u1 + T(3) * u0;
-}
-
+// (kGradU and the one-sided line formulas os2_* / os4_*: pgmg_grad_dev.h)
 template <class T, class SX, int ORDER>
 __global__ __launch_bounds__(kBlock) void k_gradient(GradArgs<SX> a)
 {
@@ -278,12 +250,9 @@ __global__ __launch_bounds__(kBlock) void k_grad_reduce(const double *partials, 
     }
 }
 
-struct GradGrid {
-    int tiles, band, bands;
-};
 // 256 pairs per workgroup in x; bands of 64 rows, shorter while the grid has fewer than ~1024
 // workgroups (k_extrap_add's rule).  A function of N alone: the partial sums depend on it
-static GradGrid grad_grid(int N)
+GradGrid grad_grid(int N)
 {
     GradGrid g;
     g.tiles = ((N - 1) / 2 + kBlock - 1) / kBlock;
@@ -296,6 +265,11 @@ int gradient_blocks(int N)
 {
     const GradGrid g = grad_grid(N);
     return g.tiles * g.bands;
+}
+
+void launch_grad_reduce(const double *partials, int np, double *sum, hipStream_t s)
+{
+    k_grad_reduce<<<dim3(1), dim3(kBlock), 0, s>>>(partials, np, sum);
 }
 
 template <class T, class SX>
@@ -315,7 +289,7 @@ void launch_gradient(const SX *x, long long Px, double *gx, double *gy, int N, d
     const dim3 grid(g.tiles, g.bands);
     if (order == 4) k_gradient<T, SX, 4><<<grid, dim3(kBlock), 0, s>>>(a);
     else k_gradient<T, SX, 2><<<grid, dim3(kBlock), 0, s>>>(a);
-    if (sum != nullptr) k_grad_reduce<<<dim3(1), dim3(kBlock), 0, s>>>(partials, g.tiles * g.bands, sum);
+    if (sum != nullptr) launch_grad_reduce(partials, g.tiles * g.bands, sum, s);
 }
 template void launch_gradient<double, double>(const double *, long long, double *, double *, int,
                                               double, int, double *, double *, hipStream_t);
@@ -327,13 +301,13 @@ double gradient_weight(int order, double scale, double h)
 }
 
 // [p, p + n) and [q, q + m) share a byte
-static bool ranges_overlap(const void *p, size_t n, const void *q, size_t m)
+bool ranges_overlap(const void *p, size_t n, const void *q, size_t m)
 {
     const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
     return a < b + m && b < a + n;
 }
 // an output of N * N doubles: device memory from its first byte to its last
-static bool device_range(const double *p, int N)
+bool device_range(const double *p, int N)
 {
     return is_device_ptr(p) && is_device_ptr(p + (size_t)N * N - 1);
 }
@@ -354,7 +328,7 @@ const char *gradient_arrays_error(const void *phi, size_t phi_bytes, const doubl
 }
 
 // the context's partial sums (np workgroups, then the total)
-static int grad_reserve(pgmg_ctx *c, int np)
+int grad_reserve(pgmg_ctx *c, int np)
 {
     if (np <= c->grad_cap) return PGMG_OK;
     if (c->grad_buf) HIPC(hipFree(c->grad_buf));

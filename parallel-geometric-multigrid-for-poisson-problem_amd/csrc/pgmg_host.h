@@ -85,6 +85,18 @@ int ext_stage_out(pgmg_ctx *c);
 int set_problem_injected(pgmg_ctx *c, const double *phi_src, long long Pphi, const double *f_src,
                          long long Pf, hipStream_t s);
 
+// the level-0 right-hand side grid was written on the device (pgmg_project's divergence): the
+// state pgmg_set_problem(the current phi, that f) leaves.  c's stream is idle
+int set_problem_rhs_on_device(pgmg_ctx *c);
+
+// --- pgmg_extrap.hip
+// points per side of the coarsest level below N
+int coarsest_n(int N, int n_coarse);
+
+// --- pgmg_gradient.hip
+// c->grad_buf holds np partial sums and their total (at grad_buf + grad_cap)
+int grad_reserve(pgmg_ctx *c, int np);
+
 // --- pgmg_monitor.hip
 // the damping pass on a level of the FMG pyramid (no norm, nothing waits); fmg_damp_reserve
 // sizes the context's side buffer and partials for a level of N points beforehand

@@ -324,5 +324,26 @@ const char *gradient_arrays_error(const void *phi, size_t phi_bytes, const doubl
 template <class T, class SX>
 void launch_gradient(const SX *x, long long Px, double *gx, double *gy, int N, double w, int order,
                      double *partials, double *sum, hipStream_t s);
+// its decomposition (tiles of 256 column pairs, `bands` bands of `band` rows), the launch that
+// adds np partial sums in index order into sum[0], and the tests of gradient_arrays_error:
+// [p, p + n) and [q, q + m) share a byte; p .. p + N * N doubles is device memory
+struct GradGrid {
+    int tiles, band, bands;
+};
+GradGrid grad_grid(int N);
+void launch_grad_reduce(const double *partials, int np, double *sum, hipStream_t s);
+bool ranges_overlap(const void *p, size_t n, const void *q, size_t m);
+bool device_range(const double *p, int N);
+
+// The projection's two passes (pgmg_project.hip; include/pgmg.h "Projection"), fp64, on
+// grad_grid(N).  launch_divergence: out = dx(u) + dy(v), the w-scaled line differences of u along
+// x and of v along y (u, v: pitch N; out: pitch Po, or null: nothing is stored); sum non-null:
+// gradient_blocks(N) partial sums of out^2 to `partials` and their total to sum[0].
+// launch_grad_update: u += gx(phi), v += gy(phi) (phi: pitch Pphi; u, v: pitch N, either may be
+// null).  No span checks here (launch_extrap's rule).
+void launch_divergence(const double *u, const double *v, double *out, long long Po, int N, double w,
+                       int order, double *partials, double *sum, hipStream_t s);
+void launch_grad_update(const double *phi, long long Pphi, double *u, double *v, int N, double w,
+                        int order, hipStream_t s);
 
 }  // namespace pgmg

@@ -168,6 +168,68 @@ int pgmg_gradient_grid(const double *d_phi, double *d_gx, double *d_gy, int N, d
     return PGMG_OK;
 }
 
+// what both projection ops refuse in N, h, order and scale (pgmg_gradient_grid's rules)
+static int project_op_check(const char *who, int N, double h, int order, double scale)
+{
+    if (N < 5 || ((N - 1) & (N - 2)) != 0 || !std::isfinite(h) || h == 0.0)
+        return set_err(PGMG_ERR_ARG, std::string(who) + ": need N = 2^k + 1 with k >= 2, a finite h "
+                                                        "that is not 0");
+    if ((order != 2 && order != 4) || !std::isfinite(scale))
+        return set_err(PGMG_ERR_ARG, std::string(who) + ": order must be 2 or 4, scale finite");
+    return PGMG_OK;
+}
+
+// out = dx(u) + dy(v) on the caller's arrays (pitch N): pgmg_project's divergence pass
+// (pgmg_project.hip), its decomposition and partial sums k_gradient's
+int pgmg_divergence_grid(const double *d_u, const double *d_v, double *d_out, int N, double h,
+                         int order, double scale, double *norm, void *stream)
+{
+    const char *const who = "pgmg_divergence_grid";
+    int e = project_op_check(who, N, h, order, scale);
+    if (e) return e;
+    if (!d_u || !d_v) return set_err(PGMG_ERR_ARG, std::string(who) + ": null u or v");
+    if (!d_out && !norm) return set_err(PGMG_ERR_ARG, std::string(who) + ": both out and norm are null");
+    const size_t bytes = (size_t)N * N * sizeof(double);
+    if (d_out && !device_range(d_out, N))
+        return set_err(PGMG_ERR_ARG, std::string(who) + ": out is not device memory");
+    if (d_out && (ranges_overlap(d_out, bytes, d_u, bytes) || ranges_overlap(d_out, bytes, d_v, bytes)))
+        return set_err(PGMG_ERR_ARG, std::string(who) + ": out overlaps u or v");
+    hipStream_t s = (hipStream_t)stream;
+    OpScratch *op = nullptr;
+    if ((e = ensure_scratch(s, 0, &op))) return e;
+    const size_t np = (size_t)gradient_blocks(N);
+    if (norm && (e = ensure_grad(s, *op, np + 1))) return e;
+    double *sum = norm ? op->grad + np : nullptr;
+    launch_divergence(d_u, d_v, d_out, N, N, gradient_weight(order, scale, h), order, op->grad, sum, s);
+    HIPC(hipGetLastError());
+    if (norm) {
+        double t = 0.0;
+        HIPC(hipMemcpyAsync(&t, sum, sizeof(t), hipMemcpyDeviceToHost, s));
+        HIPC(hipStreamSynchronize(s));
+        *norm = std::sqrt(t);
+    }
+    return PGMG_OK;
+}
+
+// u += gx(phi), v += gy(phi) on the caller's arrays (u, v: pitch N; phi: pitch_phi):
+// pgmg_project's update pass (pgmg_project.hip)
+int pgmg_gradient_add_grid(const double *d_phi, long long pitch_phi, double *d_u, double *d_v, int N,
+                           double h, int order, double scale, void *stream)
+{
+    const char *const who = "pgmg_gradient_add_grid";
+    int e = project_op_check(who, N, h, order, scale);
+    if (e) return e;
+    if (!d_phi || pitch_phi < N) return set_err(PGMG_ERR_ARG, std::string(who) + ": need phi, pitch_phi >= N");
+    // the bytes of phi the pass reads: its first element to the last of row N-1
+    const size_t pn = ((size_t)(N - 1) * (size_t)pitch_phi + (size_t)N) * sizeof(double);
+    if (const char *bad = gradient_arrays_error(d_phi, pn, d_u, d_v, N))
+        return set_err(PGMG_ERR_ARG, std::string(who) + ": " + bad);
+    launch_grad_update(d_phi, pitch_phi, d_u, d_v, N, gradient_weight(order, scale, h), order,
+                       (hipStream_t)stream);
+    HIPC(hipGetLastError());
+    return PGMG_OK;
+}
+
 // fine <- fine + C((fine(2j, 2i) - coarse) * K3) on the caller's arrays (pitches Nf and Nc): the
 // two passes of pgmg_solve_extrap's extrapolation (pgmg_extrap.hip), D dense in the stream's set
 int pgmg_extrap_grid(double *d_fine, const double *d_coarse, int Nf, void *stream)
