@@ -753,6 +753,76 @@ int pgmg_project(pgmg_ctx *ctx, const pgmg_solve_opts *o, int order, int nu, dou
                  double *d_u, double *d_v, int measure_after, pgmg_project_info *info);
 int pgmg_project_time(pgmg_ctx *ctx, int which, int order, int reps, double *ms, double *bytes);
 
+/* ---- Mixed-precision refinement ----------------------------------------------------------
+ * pgmg_solve_mixed(ctx, opts, nu, omega, info): fp64 solutions from fp32 multigrid corrections
+ * (defect correction).  The iterate phi and its residual stay in fp64 on the fp64 context ctx,
+ * which runs no cycle at all; an fp32 context it owns solves every correction equation at the
+ * fp32 rate.  fp64 context, one GPU.  Synchronous.
+ *   The child.  Owned by ctx, created on the first call, destroyed by pgmg_destroy: pgmg_create on
+ *   a copy of ctx's config -- the same N and h0 -- with precision = PGMG_PRECISION_FP32, eps =
+ *   -1.0, world 1 and PGMG_FLAG_FAST cleared, everything else equal.  Its early exits are
+ *   absolute thresholds on a scaled problem, so they are off; with them off the fp32 solve is
+ *   exactly homogeneous in a power-of-two factor on f (short of overflow and underflow).
+ *   The two passes, with s a power of two, t = 1 / s, ih = 1.0 / (h * h), evaluated left to right
+ *   as written, one rounding per operation, no fused multiply-add:
+ *     defect    r = f - ih (4x - x_l - x_r - x_u - x_d)   pgmg_monitor's r, in double, on every
+ *               g(y, x) = (float)(r * s)                  interior point: one double product, then
+ *                                                         IEEE round-to-nearest-even to fp32
+ *                                                         (overflow to Inf, gradual underflow,
+ *                                                         nothing flushed)
+ *               g = +0.0f on the frame; sqrt(sum r^2) of the unscaled r by the monitor's
+ *               decomposition and reduction: bit for bit pgmg_monitor(PGMG_MON_RESIDUAL)'s norm
+ *               of that state.  x and f are read where they lie (the level-0 grids, or the
+ *               caller's bound arrays), g is written elsewhere.  Bytes N^2 (8 + 8 + 4).
+ *     correct   x(y, x) <- x(y, x) + ((double)e(y, x) * t)     1 <= y, x <= N - 2; the frame of x
+ *               is never written (a -0.0 there stays -0.0).  Bytes N^2 (4 + 8 + 8).
+ *   The loop.  opts is pgmg_solve's: max_cycles caps the refinement steps, check_every must be 1,
+ *   cycle PGMG_CYCLE_V, monitor PGMG_MON_RESIDUAL.  rho_0 = pgmg_monitor's residual norm of the
+ *   starting phi (one extra pass per call), rho_i = r_{i-1} for i >= 1.  At check i = 0, 1, ..:
+ *     a. s_i = 2^(-ilogb(rho_i / (N - 2))), the exponent clamped to [-1022, 1022]; 1.0 when the
+ *        quotient is 0 or not finite.  The defect pass writes g_i into the child's level-0 f grid
+ *        and yields r_i (r_0 is bit for bit rho_0).
+ *     b. pgmg_solve's rule decides on r_i, in its order: non-finite, converged, stalled,
+ *        max_cycles.  On a stop nothing more is written: unlike pgmg_solve_damped, phi is exactly
+ *        the iterate info.solve.res was measured on.
+ *     c. The child's problem becomes (phi' = 0, f' = g_i): in every observable the state
+ *        pgmg_set_problem(child, zeros, g_i) leaves, a problem with a caller's f and reset
+ *        statistics.  Then pgmg_fmg_damped(child, nu, omega), asynchronous: nothing waits inside a
+ *        step but the norm of (a).  The child's sweeps are added to info.inner_sweeps.
+ *     d. The correction on phi where it lies, e = the child's phi, t = 1 / s_i.
+ *   pgmg_history holds the checks, cycle[] the steps taken before each.  info.solve.cycles is the
+ *   number of steps applied.  The fp64 residual norm falls by a factor that depends on nu alone,
+ *   not on N or f, down to fp64's floor (tests/mixed_model.py on the CPU oracle, nu = 2, omega =
+ *   0.5, N = 33 .. 257: 400 .. 3100 per step; the step that arrives at the floor gains what is
+ *   left of it; nu = 3: 4500 .. 18000; nu = 1: 25 .. 56).
+ * The entry changes phi: it drops the carry and resets the speculation history.  ctx's own sweep
+ * and early-exit statistics are untouched (it runs no cycle); ctx's eps does not matter.  phi's
+ * frame and f are bit for bit what they were.  A later pgmg_vcycle, pgmg_gradient or
+ * pgmg_solve_extrap continues from the result.  Problems set with pgmg_set_problem (the analytic
+ * f as stored, or a caller's f) and with pgmg_set_problem_device alike; a device-bound problem's
+ * arrays are read and written where they lie, the stream ordered after the caller's as
+ * pgmg_solve_extrap's is.
+ * What to ask for.  State the target as atol: the floor of the fp64 residual is ||r|| ~ 0.4 N^2
+ * 2^-52 ||f||, and rtol is relative to whatever phi the call started from.
+ * Errors, all before anything is enqueued or created.  PGMG_ERR_ARG: a null argument; invalid opts
+ * (pgmg_solve's rule); check_every != 1; a cycle other than PGMG_CYCLE_V; PGMG_MON_ERROR (call
+ * pgmg_monitor afterwards); nu < 1; omega not finite, <= 0 or > 1; a coarsest level of fewer than
+ * 5 points per side.  PGMG_ERR_STATE: before pgmg_set_problem*; world > 1; an fp32 context.
+ * pgmg_mixed_time: `reps` passes back to back between two hipEvents, after two warm ones, between
+ * ctx's phi and f and the child's grids (created if need be): which = 0 the defect pass with its
+ * reduction (s = 1, g into the child's f grid), which = 1 the correction (e = the child's phi,
+ * t = 1); mean device ms per pass and the byte models above.  Leaves phi changed, like
+ * pgmg_damp_time. */
+typedef struct pgmg_mixed_info {
+    pgmg_solve_info solve;        /* cycles = refinement steps applied, checks, reason, res0, res */
+    long long inner_sweeps;       /* the fp32 context's pgmg_stats sweeps, summed over the steps */
+    double defect_ms, inner_ms, correct_ms;   /* device time, summed over the steps */
+    double elapsed_ms;            /* host wall time of the call */
+} pgmg_mixed_info;
+int pgmg_solve_mixed(pgmg_ctx *ctx, const pgmg_solve_opts *o, int nu, double omega,
+                     pgmg_mixed_info *info);
+int pgmg_mixed_time(pgmg_ctx *ctx, int which, int reps, double *ms_per_pass, double *bytes);
+
 /* Cumulative smoother sweeps and early exits since set_problem.  The sweeps are the
  * oracle's.  The early exits are those that cut a smoother call short: the check after a
  * call's last sweep cannot change the result and is not evaluated, so where the oracle's
@@ -937,6 +1007,20 @@ int pgmg_divergence_grid(const double *d_u, const double *d_v, double *d_out, in
  * another. */
 int pgmg_gradient_add_grid(const double *d_phi, long long pitch_phi, double *d_u, double *d_v,
                            int N, double h, int order, double scale, void *stream);
+/* The two passes of pgmg_solve_mixed ("Mixed-precision refinement" above) on caller-owned device
+ * arrays at pitch N, N = 2^k + 1 with k >= 2: x and f fp64, g and e fp32.
+ * pgmg_defect_grid: g = (float)(r * scale) on the interior, +0.0f on the frame, r the fp64 residual
+ * of (x, f) at mesh width h; x and f are only read.  res_norm == NULL: asynchronous on `stream`;
+ * otherwise synchronous, and *res_norm is bit for bit pgmg_monitor(PGMG_MON_RESIDUAL)'s on a
+ * context of that N and h holding x and f; its partial sums belong to the per-stream set below.
+ * pgmg_correct_grid: x <- x + ((double)e * scale) on the interior (the caller passes 1 / s); the
+ * frame of x is never written.  Asynchronous on `stream`.
+ * Another N, h of 0 or not finite (negative is legal), a scale that is not finite or is <= 0, a
+ * null pointer, a g that is not device memory or that overlaps x or f, an e that overlaps x:
+ * PGMG_ERR_ARG, nothing enqueued. */
+int pgmg_defect_grid(const double *d_x, const double *d_f, float *d_g, int N, double h, double scale,
+                     double *res_norm, void *stream);
+int pgmg_correct_grid(double *d_x, const float *d_e, int N, double scale, void *stream);
 /* The op-level entries keep one scratch set (partial sums, flags, ping-pong buffer) per
  * stream they were called on; this waits for `stream` and frees its set (a later op on the
  * same stream allocates a fresh one).  Call it before destroying a stream the ops used. */

@@ -28,7 +28,7 @@ from ._capi import (PGMG_FLAG_LOOPBACK, PGMG_FLAG_NO_CROSS, PGMG_FLAG_NO_GRAPH,
                     PGMG_MON_RESIDUAL, PGMG_MON_ERROR, PGMG_CYCLE_V, PGMG_CYCLE_W, PGMG_CYCLE_F,
                     PGMG_STOP_CONVERGED, PGMG_STOP_MAX_CYCLES, PGMG_STOP_STALLED,
                     PGMG_STOP_NONFINITE, PgmgMonitorOut, PgmgSolveOpts, PgmgSolveInfo,
-                    PgmgExtrapInfo, PgmgProjectInfo, check, load)
+                    PgmgExtrapInfo, PgmgProjectInfo, PgmgMixedInfo, check, load)
 
 PKG_DIR = pathlib.Path(__file__).resolve().parent
 
@@ -43,7 +43,7 @@ __all__ = [
     "PGMG_MON_RESIDUAL", "PGMG_MON_ERROR", "PGMG_CYCLE_V", "PGMG_CYCLE_W", "PGMG_CYCLE_F",
     "PGMG_STOP_CONVERGED", "PGMG_STOP_MAX_CYCLES", "PGMG_STOP_STALLED", "PGMG_STOP_NONFINITE",
     "PgmgSolveOpts", "PgmgSolveInfo", "PgmgMonitorOut", "PgmgExtrapInfo",
-    "PgmgProjectInfo",
+    "PgmgProjectInfo", "PgmgMixedInfo",
 ]
 
 
@@ -471,6 +471,42 @@ class Solver:
                                          C.byref(b)), "pgmg_project_time")
         return ms.value, b.value
 
+    def solve_mixed(self, rtol=0.0, atol=0.0, max_steps=8, nu=2, damp=0.5, stall_ratio=0.0,
+                    stall_checks=2):
+        """Mixed-precision refinement of the current phi (pgmg_solve_mixed; fp64 context, one
+        GPU): phi and its residual stay in fp64, every correction is an fp32 fmg(nu, damp) of the
+        scaled residual on an fp32 context this one owns, and this context runs no cycle.  Each
+        step cuts the fp64 residual norm by a factor that depends on nu alone (~400 .. 3100 at
+        nu=2, ~4500 .. 18000 at nu=3) down to fp64's floor, ~0.4 N^2 2^-52 ||f||: state the
+        target as atol.  The stop rule is solve()'s with steps for cycles; on a stop phi is
+        exactly the iterate the last norm was measured on.  Returns the PgmgSolveInfo (cycles =
+        steps applied) with `.history` [(steps, res, nan)], `.inner_sweeps` (the fp32 context's
+        sweeps), `.defect_ms`, `.inner_ms`, `.correct_ms` (device time, summed over the steps)
+        and `.total_ms` (host wall time of the call)."""
+        o = PgmgSolveOpts()
+        check(self.lib.pgmg_solve_opts_default(C.byref(o)), "pgmg_solve_opts_default")
+        o.cycle, o.check_every, o.monitor = PGMG_CYCLE_V, 1, PGMG_MON_RESIDUAL
+        o.rtol, o.atol, o.max_cycles = rtol, atol, int(max_steps)
+        o.stall_ratio, o.stall_checks = stall_ratio, int(stall_checks)
+        mx = PgmgMixedInfo()
+        check(self.lib.pgmg_solve_mixed(self.h, C.byref(o), int(nu), float(damp), C.byref(mx)),
+              "pgmg_solve_mixed")
+        info = mx.solve
+        info.inner_sweeps = mx.inner_sweeps
+        info.defect_ms, info.inner_ms, info.correct_ms = mx.defect_ms, mx.inner_ms, mx.correct_ms
+        info.total_ms = mx.elapsed_ms
+        info.history = self.history()
+        return info
+
+    def mixed_time(self, which, reps=20):
+        """(mean device ms, algorithmic bytes) of one pass of solve_mixed over `reps` back to back
+        (pgmg_mixed_time; measurement): which=0 the defect pass with its reduction, which=1 the
+        correction.  Leaves phi changed."""
+        ms, b = C.c_double(), C.c_double()
+        check(self.lib.pgmg_mixed_time(self.h, int(which), int(reps), C.byref(ms), C.byref(b)),
+              "pgmg_mixed_time")
+        return ms.value, b.value
+
     def history(self):
         """The last solve's checks: [(cycles run before the check, res, rel_error), ...]."""
         n = C.c_int()
@@ -720,6 +756,29 @@ class _Ops:
         check(load().pgmg_damp_grid(self._ptr(x), self._ptr(f), N, float(h), float(omega),
                                     C.byref(out) if norm else None, stream), "pgmg_damp_grid")
         return out.value if norm else None
+
+    def defect(self, x, f, h, g, scale=1.0, stream=None, norm=True):
+        """g = float32(r * scale) on the interior, +0 on the frame, r = f - A x the fp64 residual
+        at mesh width h (pgmg_defect_grid): x, f N x N float64 and g N x N float32 device arrays,
+        N = 2^k + 1, k >= 2; scale finite and > 0 (a power of two keeps the scaling exact).
+        norm=True: returns sqrt(sum r^2) of the unscaled r, bit for bit Solver.monitor()'s
+        (synchronous); norm=False: returns None, asynchronous on `stream`."""
+        N = x.shape[0]
+        assert tuple(x.shape) == (N, N) and tuple(f.shape) == (N, N) and tuple(g.shape) == (N, N)
+        out = C.c_double()
+        check(load().pgmg_defect_grid(self._ptr(x), self._ptr(f), self._ptr(g), N, float(h),
+                                      float(scale), C.byref(out) if norm else None, stream),
+              "pgmg_defect_grid")
+        return out.value if norm else None
+
+    def correct(self, x, e, scale=1.0, stream=None):
+        """x += float64(e) * scale on the interior of x (pgmg_correct_grid): x N x N float64, e
+        N x N float32 device arrays; pass scale = 1 / s for a defect scaled by s.  The frame of x
+        is never written.  Asynchronous on `stream`."""
+        N = x.shape[0]
+        assert tuple(x.shape) == (N, N) and tuple(e.shape) == (N, N), (x.shape, e.shape)
+        check(load().pgmg_correct_grid(self._ptr(x), self._ptr(e), N, float(scale), stream),
+              "pgmg_correct_grid")
 
     def extrapolate(self, fine, coarse, stream=None):
         """fine <- fine + cubic((fine[::2, ::2] - coarse) * K3) on the interior of fine

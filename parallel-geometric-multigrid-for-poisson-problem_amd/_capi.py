@@ -126,6 +126,12 @@ class PgmgProjectInfo(C.Structure):
                 ("div_ms", C.c_double), ("update_ms", C.c_double), ("elapsed_ms", C.c_double)]
 
 
+class PgmgMixedInfo(C.Structure):
+    _fields_ = [("solve", PgmgSolveInfo), ("inner_sweeps", C.c_longlong),
+                ("defect_ms", C.c_double), ("inner_ms", C.c_double), ("correct_ms", C.c_double),
+                ("elapsed_ms", C.c_double)]
+
+
 # (name, restype, argtypes) for every symbol include/pgmg.h declares
 _P = C.c_void_p
 _DP = C.POINTER(C.c_double)
@@ -169,6 +175,9 @@ SIGNATURES = [
     ("pgmg_project", C.c_int, [_P, C.POINTER(PgmgSolveOpts), C.c_int, C.c_int, C.c_double, _P, _P,
                                C.c_int, C.POINTER(PgmgProjectInfo)]),
     ("pgmg_project_time", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _DP, _DP]),
+    ("pgmg_solve_mixed", C.c_int, [_P, C.POINTER(PgmgSolveOpts), C.c_int, C.c_double,
+                                   C.POINTER(PgmgMixedInfo)]),
+    ("pgmg_mixed_time", C.c_int, [_P, C.c_int, C.c_int, _DP, _DP]),
     ("pgmg_stats", C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     ("pgmg_stats_detail", C.c_int, [_P, C.POINTER(C.c_longlong)]),
     ("pgmg_last_elapsed_ms", C.c_int, [_P, _DP]),
@@ -205,6 +214,8 @@ SIGNATURES = [
                            _P]),
     ("pgmg_damp_grid", C.c_int, [_P, _P, C.c_int, C.c_double, C.c_double, _DP, _P]),
     ("pgmg_extrap_grid", C.c_int, [_P, _P, C.c_int, _P]),
+    ("pgmg_defect_grid", C.c_int, [_P, _P, _P, C.c_int, C.c_double, C.c_double, _DP, _P]),
+    ("pgmg_correct_grid", C.c_int, [_P, _P, C.c_int, C.c_double, _P]),
     ("pgmg_gradient_grid", C.c_int, [_P, _P, _P, C.c_int, C.c_double, C.c_int, C.c_double, _DP,
                                      _P]),
     ("pgmg_divergence_grid", C.c_int, [_P, _P, _P, C.c_int, C.c_double, C.c_int, C.c_double, _DP,

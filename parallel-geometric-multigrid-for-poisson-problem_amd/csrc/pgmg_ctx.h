@@ -274,6 +274,11 @@ struct pgmg_ctx {
     // made on the first call that needs them
     hipEvent_t pj_ev0 = nullptr, pj_ev1 = nullptr;
     double *pj_out = nullptr;
+    // pgmg_solve_mixed (pgmg_mixed.hip), made on its first call: the fp32 context of the same N
+    // and mesh width this one owns, and the event pairs around the defect pass, the child's
+    // solve (on the child's stream) and the correction
+    pgmg_ctx *mx_child = nullptr;
+    hipEvent_t mx_ev[6] = {};
 };
 
 namespace pgmg {

@@ -138,6 +138,9 @@ int pgmg_destroy(pgmg_ctx *c)
         unregister_alloc(c->ex_D);
         (void)hipFree(c->ex_D);
     }
+    if (c->mx_child) (void)pgmg_destroy(c->mx_child);
+    for (hipEvent_t e : c->mx_ev)
+        if (e) (void)hipEventDestroy(e);
     if (c->grad_buf) (void)hipFree(c->grad_buf);
     if (c->grad_out) {
         unregister_alloc(c->grad_out);
@@ -637,6 +640,37 @@ int pgmg::set_problem_rhs_on_device(pgmg_ctx *c)
     c->analytic = false;
     PGMG_TRY(drop_graph_of_other_rhs(c, old));
     return problem_reset(c);
+}
+
+// The fp32 sibling for pgmg_solve_mixed's child (pgmg_mixed.hip): its level-0 f grid holds the
+// scaled defect, written on the parent's stream, which the host has waited for.  The state
+// pgmg_set_problem(zeros, that f) leaves -- phi zero, its (zero) frame in B and S, a problem with a
+// caller's f, the statistics and the speculation history reset, the carry dropped -- but enqueued
+// on c's own stream: the memsets run in stream order before whatever the caller enqueues next,
+// and nothing waits.  The interiors of B and S are scratch no pass reads before writing.
+int pgmg::set_problem_zero_rhs_on_device_f32(pgmg_ctx *c)
+{
+    if (!c->fp32 || c->comm)
+        return set_err(PGMG_ERR_STATE, "device right-hand side (fp32): fp32, one GPU only");
+    Level &L = c->lv[0];
+    // (rows 0 .. N of a level-0 grid are one contiguous range: see pgmg_set_problem)
+    const size_t bytes = (size_t)L.P * L.es * (size_t)L.N;
+    HIPC(hipMemsetAsync(row_ptr(L.A, 0, L.P, L.es), 0, bytes, c->s));
+    for (const Grid *g : {&L.B, &c->S})
+        if (g->base) launch_zero_frame(G<float>(*g), L.P, L.N, c->s);
+    HIPC(hipMemsetAsync(c->stats, 0, 4 * sizeof(unsigned long long), c->s));
+    HIPC(hipGetLastError());
+    const double *const old = c->rgfx;
+    c->ext_phi = nullptr;
+    c->ext_f = nullptr;
+    c->gen_rhs = false;
+    c->rgfx = c->rgsy = nullptr;
+    c->analytic = false;
+    PGMG_TRY(drop_graph_of_other_rhs(c, old));
+    c->have_problem = true;
+    c->carry = false;
+    c->hist.reset(c->nb);
+    return PGMG_OK;
 }
 
 // ---------------------------------------------------------------------------

@@ -88,6 +88,10 @@ int set_problem_injected(pgmg_ctx *c, const double *phi_src, long long Pphi, con
 // the level-0 right-hand side grid was written on the device (pgmg_project's divergence): the
 // state pgmg_set_problem(the current phi, that f) leaves.  c's stream is idle
 int set_problem_rhs_on_device(pgmg_ctx *c);
+// its fp32 sibling (pgmg_solve_mixed's child): the level-0 f grid of the fp32, one-GPU,
+// context-owned c holds the new f (written on another stream, which the host has waited for);
+// phi becomes zero.  Enqueued on c's stream: nothing waits
+int set_problem_zero_rhs_on_device_f32(pgmg_ctx *c);
 
 // --- pgmg_extrap.hip
 // points per side of the coarsest level below N
@@ -102,6 +106,9 @@ int grad_reserve(pgmg_ctx *c, int np);
 // sizes the context's side buffer and partials for a level of N points beforehand
 int fmg_damp_reserve(pgmg_ctx *c, int N);
 int fmg_damp_level(pgmg_ctx *c, const Grid &u, const Grid &f, const Level &L, double omega, bool gen);
+// c->mon_buf holds the partials of np workgroups and the three totals (at mon_buf + 3 * mon_cap);
+// side: bytes of the damping pass's side buffer (0: none needed)
+int mon_reserve(pgmg_ctx *c, int np, size_t side);
 
 // the tail launch's arguments every caller shares (visits, x0_from_global, fmg_*: the caller's)
 template <class T>

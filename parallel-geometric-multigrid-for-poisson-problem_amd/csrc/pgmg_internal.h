@@ -302,6 +302,28 @@ void launch_damp_grid(T *x, long long Px, const T *f, long long Pf, int N, doubl
                       double omega, const double *gfx, const double *gsy, double *partials, T *side,
                       double *sums, hipStream_t s);
 
+// The monitor's decomposition (pgmg_monitor.hip), shared by the passes that yield its sums:
+// tiles of kMonTile columns, bands of kMonBand rows, kMonU rows of loads in flight per wave;
+// damp_grid_blocks(N) workgroups on a whole grid.  launch_mon_reduce: k_mon_reduce's launch, the
+// index-order sum of np workgroups' partials (3 each) into out[0 .. 2].
+constexpr int kMonBand = 64;           // rows per workgroup
+constexpr int kMonTile = 2 * kBlock;   // columns per workgroup (a column pair per lane)
+constexpr int kMonU = 4;               // rows in flight per wave
+void launch_mon_reduce(const double *partials, int np, double *out, hipStream_t s);
+
+// Mixed-precision refinement (pgmg_mixed.hip; include/pgmg.h "Mixed-precision refinement").
+// launch_defect: g = (float)(r * scale) on the interior, +0 on the frame, r the monitor's fp64
+// residual of (x, f); partials: 3 * damp_grid_blocks(N) doubles, the monitor's partial sums of
+// r^2; sums non-null: one more launch, sums[0] = their total.  launch_correct: x += (double)e * t
+// on the interior.  Element (0, 0) and pitch (elements) of every array.  No span checks here
+// (launch_extrap's rule).  device_range_f32: p .. p + N * N floats is device memory.
+void launch_defect(const double *x, long long Px, const double *f, long long Pf, float *g,
+                   long long Pg, int N, double ih, double scale, double *partials, double *sums,
+                   hipStream_t s);
+void launch_correct(double *x, long long Px, const float *e, long long Pe, int N, double t,
+                    hipStream_t s);
+bool device_range_f32(const float *p, int N);
+
 // Richardson extrapolation (pgmg_extrap.hip; include/pgmg.h "Fourth-order solves"), fp64.
 // launch_inject: dst(j, i) = src(2j, 2i) on n x n destination points.  launch_extrap: the two
 // passes fine <- fine + C((fine(2j, 2i) - coarse) * K3) on a fine grid of 2 Nc - 1 points per

@@ -48,9 +48,7 @@ using namespace pgmg;
 
 namespace pgmg {
 
-constexpr int kMonBand = 64;           // rows per workgroup
-constexpr int kMonTile = 2 * kBlock;   // columns per workgroup (a column pair per lane)
-constexpr int kMonU = 4;               // rows in flight per wave
+// (kMonBand, kMonTile, kMonU: pgmg_internal.h, shared with k_defect of pgmg_mixed.hip)
 
 constexpr unsigned kMonRes = PGMG_MON_RESIDUAL, kMonErr = PGMG_MON_ERROR;
 constexpr unsigned kMonGen = 4u;       // f regenerated from the sine tables (not streamed)
@@ -405,8 +403,15 @@ template void launch_damp_grid<float>(float *, long long, const float *, long lo
                                       double, double, const double *, const double *, double *,
                                       float *, double *, hipStream_t);
 
+// k_mon_reduce on np workgroups' partials, for the passes that write the monitor's partial sums
+// on the monitor's decomposition (k_defect, pgmg_mixed.hip)
+void launch_mon_reduce(const double *partials, int np, double *out, hipStream_t s)
+{
+    k_mon_reduce<<<dim3(1), dim3(kBlock), 0, s>>>(partials, np, out);
+}
+
 // the context's partials (np workgroups) and, for a damping pass, its side buffer (side bytes)
-static int mon_reserve(pgmg_ctx *c, int np, size_t side)
+int mon_reserve(pgmg_ctx *c, int np, size_t side)
 {
     if (side > c->mon_side_bytes) {
         if (c->mon_side) HIPC(hipFree(c->mon_side));

@@ -276,6 +276,65 @@ int pgmg_damp_grid(double *d_x, const double *d_f, int N, double h, double omega
     return PGMG_OK;
 }
 
+// what both refinement ops refuse in N and scale
+static int mixed_op_check(const char *who, int N, double scale)
+{
+    if (N < 5 || ((N - 1) & (N - 2)) != 0)
+        return set_err(PGMG_ERR_ARG, std::string(who) + ": need N = 2^k + 1 with k >= 2");
+    if (!std::isfinite(scale) || !(scale > 0.0))
+        return set_err(PGMG_ERR_ARG, std::string(who) + ": scale must be finite and > 0");
+    return PGMG_OK;
+}
+
+// g = (float)(r * scale), r the fp64 residual of (x, f), on the caller's arrays (pitch N):
+// pgmg_solve_mixed's defect pass (pgmg_mixed.hip), its decomposition and partial sums the
+// monitor's of a context of that N
+int pgmg_defect_grid(const double *d_x, const double *d_f, float *d_g, int N, double h, double scale,
+                     double *res_norm, void *stream)
+{
+    const char *const who = "pgmg_defect_grid";
+    int e = mixed_op_check(who, N, scale);
+    if (e) return e;
+    if (!std::isfinite(h) || h == 0.0)
+        return set_err(PGMG_ERR_ARG, std::string(who) + ": need a finite h that is not 0");
+    if (!d_x || !d_f || !d_g) return set_err(PGMG_ERR_ARG, std::string(who) + ": null x, f or g");
+    const size_t bytes = (size_t)N * N * sizeof(double), gbytes = (size_t)N * N * sizeof(float);
+    if (!device_range_f32(d_g, N))
+        return set_err(PGMG_ERR_ARG, std::string(who) + ": g is not device memory");
+    if (ranges_overlap(d_g, gbytes, d_x, bytes) || ranges_overlap(d_g, gbytes, d_f, bytes))
+        return set_err(PGMG_ERR_ARG, std::string(who) + ": g overlaps x or f");
+    hipStream_t s = (hipStream_t)stream;
+    OpScratch *op = nullptr;
+    if ((e = ensure_scratch(s, 0, &op))) return e;
+    const size_t np = (size_t)damp_grid_blocks(N);
+    if ((e = ensure_mon(s, *op, 3 * np + 3))) return e;
+    double *sums = res_norm ? op->mon + 3 * np : nullptr;
+    launch_defect(d_x, N, d_f, N, d_g, N, N, 1.0 / (h * h), scale, op->mon, sums, s);
+    HIPC(hipGetLastError());
+    if (res_norm) {
+        double t = 0.0;
+        HIPC(hipMemcpyAsync(&t, sums, sizeof(t), hipMemcpyDeviceToHost, s));
+        HIPC(hipStreamSynchronize(s));
+        *res_norm = std::sqrt(t);
+    }
+    return PGMG_OK;
+}
+
+// x += (double)e * scale on the interior of the caller's arrays (pitch N): pgmg_solve_mixed's
+// correction pass (pgmg_mixed.hip)
+int pgmg_correct_grid(double *d_x, const float *d_e, int N, double scale, void *stream)
+{
+    const char *const who = "pgmg_correct_grid";
+    int e = mixed_op_check(who, N, scale);
+    if (e) return e;
+    if (!d_x || !d_e) return set_err(PGMG_ERR_ARG, std::string(who) + ": null x or e");
+    if (ranges_overlap(d_e, (size_t)N * N * sizeof(float), d_x, (size_t)N * N * sizeof(double)))
+        return set_err(PGMG_ERR_ARG, std::string(who) + ": e overlaps x");
+    launch_correct(d_x, N, d_e, N, N, scale, (hipStream_t)stream);
+    HIPC(hipGetLastError());
+    return PGMG_OK;
+}
+
 int pgmg_jacobi(double *d_x, double *d_tmp, const double *d_f, int H, int W, double h, int v,
                 double eps, int *sweeps_done, void *stream)
 {
