@@ -753,6 +753,84 @@ int pgmg_project(pgmg_ctx *ctx, const pgmg_solve_opts *o, int order, int nu, dou
                  double *d_u, double *d_v, int measure_after, pgmg_project_info *info);
 int pgmg_project_time(pgmg_ctx *ctx, int which, int order, int reps, double *ms, double *bytes);
 
+/* ---- Vorticity transport ---------------------------------------------------------------------
+ * pgmg_vorticity_step(ctx, opts, omega, dt, nu, mode, walls, nsteps, info): 2D incompressible flow
+ * in streamfunction-vorticity form, on the device, without a host round trip.  With u = psi_y,
+ * v = -psi_x and w = v_x - u_y the flow obeys
+ *     w_t + u w_x + v w_y = nu lap(w),      -lap(psi) = w,
+ * and the second equation is exactly the problem every solve of the library solves: the
+ * right-hand side f is the vorticity w and phi is the streamfunction psi, constant on solid walls
+ * (a Dirichlet frame).  The velocity is divergence free by construction; no-slip walls and a
+ * moving lid enter through the wall vorticity alone.  The state is the context's own problem:
+ * start it with pgmg_set_problem(psi0, w0) (zeros: a cavity at rest).  fp64, one GPU.
+ * Synchronous.  Element (j, i) is at x = i h, y = j h; h is the context's finest mesh width (a
+ * negative h is used as written).  The expressions follow "Gradient of the solution" above:
+ * evaluated left to right as written, one rounding per operation, no fused multiply-add.  P is
+ * psi, W is w (not the solve's damping factor `omega`).
+ *   The step, on the interior 1 <= y, x <= N - 2, with wgt = 0.5 / h and ih = 1.0 / (h * h):
+ *     px  = (P[y][x+1] - P[y][x-1]) * wgt      py = (P[y+1][x] - P[y-1][x]) * wgt
+ *     wx  = (W[y][x+1] - W[y][x-1]) * wgt      wy = (W[y+1][x] - W[y-1][x]) * wgt
+ *     adv = py * wx - px * wy                            two products, one subtraction
+ *     lap = (W[y][x-1] + W[y][x+1] + W[y-1][x] + W[y+1][x] - 4.0 * W[y][x]) * ih
+ *     out[y][x] = W[y][x] + dt * (nu * lap - adv)        nu * lap, - adv, dt * (..), W + ..
+ *   Every term comes from the P and W of before the pass.  The frame of out is the frame of W,
+ *   word for word (a -0.0 stays -0.0).  The pass can also yield vmax = the maximum over the
+ *   interior of |px| + |py|, NaN terms skipped as fmax skips them (per-workgroup maxima combined
+ *   by a second launch; no atomics); cfl = dt * vmax / |h|.  16 B read and 8 B written per point.
+ *   The wall pass, on the frame of W, with c = 2.0 * ih, d = 2.0 / h and the wall speeds walls[] =
+ *   { ub, ut, vl, vr }: u on y = 0 and on y = (N-1) h, v on x = 0 and on x = (N-1) h (Thom's
+ *   formula; psi's frame is read, not assumed 0):
+ *     W[0][x]   = (P[0][x]   - P[1][x])   * c + ub * d      1 <= x <= N - 2
+ *     W[N-1][x] = (P[N-1][x] - P[N-2][x]) * c - ut * d
+ *     W[y][0]   = (P[y][0]   - P[y][1])   * c - vl * d      1 <= y <= N - 2
+ *     W[y][N-1] = (P[y][N-1] - P[y][N-2]) * c + vr * d
+ *     the four corners = +0.0                               (no interior stencil reads a corner)
+ *   mode PGMG_WALL_FREE writes +0.0 on the whole frame instead (free slip; walls[] must still be
+ *   finite).  Nothing in the solver reads f's frame.
+ * Per step:
+ *   1. The wall pass on f's frame, from the current phi.
+ *   2. The step, f and phi read where they lie, into a scratch grid of f's shape (allocated on the
+ *      first call) that is then copied onto f on the stream.  The context's problem is then one
+ *      with a caller's f, in every observable the state pgmg_set_problem(the current phi, that f)
+ *      leaves -- as after pgmg_project's step 1: the statistics and the speculation history start
+ *      over and the carry is dropped.
+ *   3. pgmg_solve_damped(ctx, opts, omega, &info->last), warm-started from the previous psi.  Its
+ *      stop reason is reported, never acted on.  phi's frame is never written.
+ * After the last step one more wall pass runs, so the returned f's frame belongs to the returned
+ * phi, and the first wall pass of the next call reproduces it bit for bit: nsteps = 3 gives the
+ * bits of three calls of one step.  A later pgmg_vcycle or pgmg_gradient continues from (phi, f);
+ * the velocity is pgmg_gradient at order 2: u = gy at scale 1, v = gx at scale -1.
+ * Stability is the caller's business: explicit Euler with central differences needs about
+ * info->cfl <= 1 and info->diffusion = 4 nu dt / h^2 <= 1 (and a cell Reynolds number
+ * |u| h / nu of at most about 2 for a monotone solution).  A non-finite cfl is no error.  The
+ * scheme is first order in time and second order in space.  The model is tests/vort_model.py.
+ * Errors, all before anything is written.  PGMG_ERR_ARG: a null argument; invalid opts
+ * (pgmg_solve's rule); PGMG_MON_ERROR in opts; omega not finite, <= 0 or > 1; dt not finite or
+ * <= 0; nu not finite or < 0; a mode other than the two; a wall speed that is not finite; nsteps
+ * < 1.  PGMG_ERR_STATE: before pgmg_set_problem; world > 1; an fp32 context; a device-bound
+ * problem (pgmg_set_problem_device: its f is the caller's const array).
+ * pgmg_vorticity_time: `reps` passes back to back between two hipEvents, after two warm ones, on
+ * three context-owned scratch arrays allocated on the first call (24 N^2 bytes): which = 0 the
+ * step with its copy back (40 N^2 bytes), which = 1 the step with vmax, both launches (24 N^2);
+ * mean device ms per pass and those byte models.  Neither phi nor f is written.  fp64, one GPU,
+ * after pgmg_set_problem*. */
+#define PGMG_WALL_NOSLIP 0
+#define PGMG_WALL_FREE 1
+typedef struct pgmg_vort_info {
+    int steps;                    /* steps taken */
+    long long cycles, sweeps;     /* summed over the steps' solves */
+    pgmg_solve_info last;         /* the last step's damped solve */
+    int worst_reason;             /* the largest final residual norm of any step's solve (a NaN */
+    double worst_res;             /* counts as the largest), and that solve's stop reason */
+    double cfl, diffusion;        /* last step: dt * vmax / |h|;  4 * nu * dt / (h * h) */
+    double step_ms, solve_ms;     /* summed: device time of the wall and step passes with the copy;
+                                     the solves' elapsed_ms */
+    double elapsed_ms;            /* host wall time of the call */
+} pgmg_vort_info;
+int pgmg_vorticity_step(pgmg_ctx *ctx, const pgmg_solve_opts *o, double omega, double dt, double nu,
+                        int mode, const double walls[4], int nsteps, pgmg_vort_info *info);
+int pgmg_vorticity_time(pgmg_ctx *ctx, int which, int reps, double *ms_per_pass, double *bytes);
+
 /* ---- Mixed-precision refinement ----------------------------------------------------------
  * pgmg_solve_mixed(ctx, opts, nu, omega, info): fp64 solutions from fp32 multigrid corrections
  * (defect correction).  The iterate phi and its residual stay in fp64 on the fp64 context ctx,
@@ -1007,6 +1085,22 @@ int pgmg_divergence_grid(const double *d_u, const double *d_v, double *d_out, in
  * another. */
 int pgmg_gradient_add_grid(const double *d_phi, long long pitch_phi, double *d_u, double *d_v,
                            int N, double h, int order, double scale, void *stream);
+/* The two passes of pgmg_vorticity_step ("Vorticity transport" above) on caller-owned device
+ * arrays of doubles at pitch N, N = 2^k + 1 with k >= 2.
+ * pgmg_vorticity_grid: d_out = the step of d_w under d_psi on the interior, d_w's frame on the
+ * frame; d_psi and d_w are only read, d_out must not overlap either.  vmax == NULL: asynchronous
+ * on `stream`; otherwise synchronous, *vmax = the maximum of |px| + |py| over the interior (its
+ * per-workgroup partials belong to the per-stream set below).
+ * pgmg_wall_vorticity_grid: the wall pass in place on d_w's frame, from d_psi (only read; the two
+ * must not overlap); mode PGMG_WALL_NOSLIP or PGMG_WALL_FREE, walls = { ub, ut, vl, vr }.
+ * Asynchronous on `stream`.
+ * Another N, h of 0 or not finite (negative is legal), dt not finite or <= 0, nu not finite or
+ * < 0, another mode, a wall speed that is not finite, a null pointer, an output that is not device
+ * memory, overlapping arrays: PGMG_ERR_ARG, nothing enqueued. */
+int pgmg_vorticity_grid(const double *d_psi, const double *d_w, double *d_out, int N, double h,
+                        double dt, double nu, double *vmax, void *stream);
+int pgmg_wall_vorticity_grid(const double *d_psi, double *d_w, int N, double h, int mode,
+                             const double walls[4], void *stream);
 /* The two passes of pgmg_solve_mixed ("Mixed-precision refinement" above) on caller-owned device
  * arrays at pitch N, N = 2^k + 1 with k >= 2: x and f fp64, g and e fp32.
  * pgmg_defect_grid: g = (float)(r * scale) on the interior, +0.0f on the frame, r the fp64 residual

@@ -28,7 +28,8 @@ from ._capi import (PGMG_FLAG_LOOPBACK, PGMG_FLAG_NO_CROSS, PGMG_FLAG_NO_GRAPH,
                     PGMG_MON_RESIDUAL, PGMG_MON_ERROR, PGMG_CYCLE_V, PGMG_CYCLE_W, PGMG_CYCLE_F,
                     PGMG_STOP_CONVERGED, PGMG_STOP_MAX_CYCLES, PGMG_STOP_STALLED,
                     PGMG_STOP_NONFINITE, PgmgMonitorOut, PgmgSolveOpts, PgmgSolveInfo,
-                    PgmgExtrapInfo, PgmgProjectInfo, PgmgMixedInfo, check, load)
+                    PgmgExtrapInfo, PgmgProjectInfo, PgmgMixedInfo, PgmgVortInfo,
+                    PGMG_WALL_NOSLIP, PGMG_WALL_FREE, check, load)
 
 PKG_DIR = pathlib.Path(__file__).resolve().parent
 
@@ -43,7 +44,7 @@ __all__ = [
     "PGMG_MON_RESIDUAL", "PGMG_MON_ERROR", "PGMG_CYCLE_V", "PGMG_CYCLE_W", "PGMG_CYCLE_F",
     "PGMG_STOP_CONVERGED", "PGMG_STOP_MAX_CYCLES", "PGMG_STOP_STALLED", "PGMG_STOP_NONFINITE",
     "PgmgSolveOpts", "PgmgSolveInfo", "PgmgMonitorOut", "PgmgExtrapInfo",
-    "PgmgProjectInfo", "PgmgMixedInfo",
+    "PgmgProjectInfo", "PgmgMixedInfo", "PgmgVortInfo", "PGMG_WALL_NOSLIP", "PGMG_WALL_FREE",
 ]
 
 
@@ -471,6 +472,61 @@ class Solver:
                                          C.byref(b)), "pgmg_project_time")
         return ms.value, b.value
 
+    def vorticity_step(self, dt, nu, walls=(0.0, 0.0, 0.0, 0.0), free=False, nsteps=1, damp=0.5,
+                       atol=0.0, rtol=0.0, max_cycles=30, check_every=1):
+        """`nsteps` explicit Euler steps of 2D incompressible flow in streamfunction-vorticity form
+        (pgmg_vorticity_step): the context's phi is the streamfunction psi (u = psi_y, v = -psi_x)
+        and its f the vorticity; start with set_problem(psi0, omega0) (zeros: a cavity at rest).
+        Per step: f's frame from psi by Thom's formula with the wall speeds walls = (u on y = 0,
+        u on y = a, v on x = 0, v on x = a) -- or +0.0 with free=True (free slip) --, then
+        f <- f + dt (nu lap(f) - (psi_y f_x - psi_x f_y)) on the interior, then the damped solve
+        of -lap(psi) = f warm-started from the previous psi (state the target as atol, create the
+        Solver with eps < 0).  Stability is the caller's business: keep `.cfl` below about 1 and
+        `.diffusion` = 4 nu dt / h^2 at most 1.  Returns a namespace: steps, cycles and sweeps
+        (summed), last (the last step's PgmgSolveInfo), worst_res and worst_reason, cfl, diffusion,
+        step_ms, solve_ms, elapsed_ms, history (the last solve's checks).  fp64, one GPU,
+        context-owned problems."""
+        from types import SimpleNamespace
+        o = PgmgSolveOpts()
+        check(self.lib.pgmg_solve_opts_default(C.byref(o)), "pgmg_solve_opts_default")
+        o.rtol, o.atol, o.max_cycles, o.check_every = rtol, atol, int(max_cycles), int(check_every)
+        w = (C.c_double * 4)(*(float(x) for x in walls))
+        info = PgmgVortInfo()
+        check(self.lib.pgmg_vorticity_step(self.h, C.byref(o), float(damp), float(dt), float(nu),
+                                           PGMG_WALL_FREE if free else PGMG_WALL_NOSLIP, w,
+                                           int(nsteps), C.byref(info)), "pgmg_vorticity_step")
+        out = SimpleNamespace(**{name: getattr(info, name) for name, _ in PgmgVortInfo._fields_})
+        out.history = self.history()
+        return out
+
+    def vorticity_time(self, which, reps=20):
+        """(mean device ms, algorithmic bytes) of one pass of vorticity_step over `reps` back to
+        back on context-owned arrays (pgmg_vorticity_time; measurement): which=0 the step with
+        its copy back, which=1 the step with the velocity maximum.  Leaves phi and f alone."""
+        ms, b = C.c_double(), C.c_double()
+        check(self.lib.pgmg_vorticity_time(self.h, int(which), int(reps), C.byref(ms), C.byref(b)),
+              "pgmg_vorticity_time")
+        return ms.value, b.value
+
+    def velocity(self, u=None, v=None):
+        """(u, v) = (psi_y, -psi_x) of the current phi read as a streamfunction: two gradient
+        passes at order 2 with one output each (pgmg_gradient: gy into u at scale 1, gx into v at
+        scale -1).  u, v: N x N float64 CUDA tensors (allocated when None)."""
+        import torch
+        N = self.N
+        dev = torch.device("cuda", int(self.cfg.device))
+        if u is None:
+            u = torch.empty((N, N), dtype=torch.float64, device=dev)
+        if v is None:
+            v = torch.empty((N, N), dtype=torch.float64, device=dev)
+        for t in (u, v):
+            if not (t.is_cuda and t.dtype == torch.float64 and tuple(t.shape) == (N, N)
+                    and t.is_contiguous()):
+                raise ValueError("u and v must be contiguous N x N float64 CUDA tensors")
+        check(self.lib.pgmg_gradient(self.h, 2, 1.0, None, _dptr(u), None), "pgmg_gradient")
+        check(self.lib.pgmg_gradient(self.h, 2, -1.0, _dptr(v), None, None), "pgmg_gradient")
+        return u, v
+
     def solve_mixed(self, rtol=0.0, atol=0.0, max_steps=8, nu=2, damp=0.5, stall_ratio=0.0,
                     stall_checks=2):
         """Mixed-precision refinement of the current phi (pgmg_solve_mixed; fp64 context, one
@@ -839,6 +895,31 @@ class _Ops:
         check(load().pgmg_gradient_add_grid(self._ptr(phi), N, self._ptr(u), self._ptr(v), N,
                                             float(h), int(order), float(scale), stream),
               "pgmg_gradient_add_grid")
+
+    def vorticity_step(self, psi, w, out, h, dt, nu, vmax=False, stream=None):
+        """out = w + dt (nu lap(w) - (psi_y w_x - psi_x w_y)) on the interior, w's frame on the
+        frame (pgmg_vorticity_grid): N x N float64 device arrays, N = 2^k + 1, k >= 2; h finite
+        and not 0; out must not overlap psi or w.  vmax=False: returns out, asynchronous on
+        `stream`; vmax=True: returns (out, max |psi_x| + |psi_y| over the interior), synchronous."""
+        N = psi.shape[0]
+        assert tuple(psi.shape) == (N, N) and tuple(w.shape) == (N, N) and tuple(out.shape) == (N, N)
+        m = C.c_double()
+        check(load().pgmg_vorticity_grid(self._ptr(psi), self._ptr(w), self._ptr(out), N, float(h),
+                                         float(dt), float(nu), C.byref(m) if vmax else None, stream),
+              "pgmg_vorticity_grid")
+        return (out, m.value) if vmax else out
+
+    def wall_vorticity(self, psi, w, h, walls=(0.0, 0.0, 0.0, 0.0), free=False, stream=None):
+        """The frame of w from psi by Thom's formula, in place (pgmg_wall_vorticity_grid): walls =
+        (u on y = 0, u on y = a, v on x = 0, v on x = a); free=True writes +0.0 on the whole frame
+        (free slip).  The corners become +0.0.  Asynchronous on `stream`."""
+        N = psi.shape[0]
+        assert tuple(psi.shape) == (N, N) and tuple(w.shape) == (N, N), (psi.shape, w.shape)
+        ws = (C.c_double * 4)(*(float(x) for x in walls))
+        check(load().pgmg_wall_vorticity_grid(self._ptr(psi), self._ptr(w), N, float(h),
+                                              PGMG_WALL_FREE if free else PGMG_WALL_NOSLIP, ws,
+                                              stream), "pgmg_wall_vorticity_grid")
+        return w
 
     def release(self, stream=None):
         """Wait for `stream` and free the scratch set the ops keep for it (pgmg_ops_release)."""

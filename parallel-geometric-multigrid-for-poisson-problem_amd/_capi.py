@@ -56,6 +56,8 @@ PGMG_STOP_CONVERGED = 1
 PGMG_STOP_MAX_CYCLES = 2
 PGMG_STOP_STALLED = 3
 PGMG_STOP_NONFINITE = 4
+PGMG_WALL_NOSLIP = 0
+PGMG_WALL_FREE = 1
 
 
 # pgmg_host_transport (include/pgmg.h): the caller's message functions
@@ -126,6 +128,13 @@ class PgmgProjectInfo(C.Structure):
                 ("div_ms", C.c_double), ("update_ms", C.c_double), ("elapsed_ms", C.c_double)]
 
 
+class PgmgVortInfo(C.Structure):
+    _fields_ = [("steps", C.c_int), ("cycles", C.c_longlong), ("sweeps", C.c_longlong),
+                ("last", PgmgSolveInfo), ("worst_reason", C.c_int), ("worst_res", C.c_double),
+                ("cfl", C.c_double), ("diffusion", C.c_double), ("step_ms", C.c_double),
+                ("solve_ms", C.c_double), ("elapsed_ms", C.c_double)]
+
+
 class PgmgMixedInfo(C.Structure):
     _fields_ = [("solve", PgmgSolveInfo), ("inner_sweeps", C.c_longlong),
                 ("defect_ms", C.c_double), ("inner_ms", C.c_double), ("correct_ms", C.c_double),
@@ -175,6 +184,9 @@ SIGNATURES = [
     ("pgmg_project", C.c_int, [_P, C.POINTER(PgmgSolveOpts), C.c_int, C.c_int, C.c_double, _P, _P,
                                C.c_int, C.POINTER(PgmgProjectInfo)]),
     ("pgmg_project_time", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _DP, _DP]),
+    ("pgmg_vorticity_step", C.c_int, [_P, C.POINTER(PgmgSolveOpts), C.c_double, C.c_double,
+                                      C.c_double, C.c_int, _DP, C.c_int, C.POINTER(PgmgVortInfo)]),
+    ("pgmg_vorticity_time", C.c_int, [_P, C.c_int, C.c_int, _DP, _DP]),
     ("pgmg_solve_mixed", C.c_int, [_P, C.POINTER(PgmgSolveOpts), C.c_int, C.c_double,
                                    C.POINTER(PgmgMixedInfo)]),
     ("pgmg_mixed_time", C.c_int, [_P, C.c_int, C.c_int, _DP, _DP]),
@@ -222,6 +234,9 @@ SIGNATURES = [
                                        _P]),
     ("pgmg_gradient_add_grid", C.c_int, [_P, C.c_longlong, _P, _P, C.c_int, C.c_double, C.c_int,
                                          C.c_double, _P]),
+    ("pgmg_vorticity_grid", C.c_int, [_P, _P, _P, C.c_int, C.c_double, C.c_double, C.c_double, _DP,
+                                      _P]),
+    ("pgmg_wall_vorticity_grid", C.c_int, [_P, _P, C.c_int, C.c_double, C.c_int, _DP, _P]),
     ("pgmg_ops_release", C.c_int, [_P]),
     ("pgmg_device_alloc", C.c_int, [C.POINTER(_P), C.c_size_t]),
     ("pgmg_device_free", C.c_int, [_P]),

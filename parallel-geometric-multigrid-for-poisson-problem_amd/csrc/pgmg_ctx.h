@@ -279,6 +279,13 @@ struct pgmg_ctx {
     // solve (on the child's stream) and the correction
     pgmg_ctx *mx_child = nullptr;
     hipEvent_t mx_ev[6] = {};
+    // pgmg_vorticity_step (pgmg_vorticity.hip), made on the first call that needs them: the grid
+    // of f's shape the step is written into before it is copied onto f, the events around the
+    // passes, and pgmg_vorticity_time's three scratch arrays (N * N doubles each, a registered
+    // allocation)
+    pgmg::Grid vt_out;
+    hipEvent_t vt_ev[2] = {};
+    double *vt_scr = nullptr;
 };
 
 namespace pgmg {

@@ -150,6 +150,13 @@ int pgmg_destroy(pgmg_ctx *c)
         unregister_alloc(c->pj_out);
         (void)hipFree(c->pj_out);
     }
+    free_grid(c->vt_out);
+    if (c->vt_scr) {
+        unregister_alloc(c->vt_scr);
+        (void)hipFree(c->vt_scr);
+    }
+    for (hipEvent_t e : c->vt_ev)
+        if (e) (void)hipEventDestroy(e);
     if (c->pj_ev0) (void)hipEventDestroy(c->pj_ev0);
     if (c->pj_ev1) (void)hipEventDestroy(c->pj_ev1);
     if (c->ex_ev0) (void)hipEventDestroy(c->ex_ev0);

@@ -101,6 +101,23 @@ int coarsest_n(int N, int n_coarse);
 // c->grad_buf holds np partial sums and their total (at grad_buf + grad_cap)
 int grad_reserve(pgmg_ctx *c, int np);
 
+// --- pgmg_vorticity.hip
+// The two passes of the vorticity transport (include/pgmg.h "Vorticity transport"), fp64, element
+// (0, 0) and pitch (elements) of every array.  launch_vort_step: out = the explicit Euler step of
+// omega (w) under psi on the interior, w's frame on the frame, on grad_grid(N); vmax non-null:
+// gradient_blocks(N) per-workgroup maxima of |psi_x| + |psi_y| to `partials` and one more launch
+// their maximum to vmax[0].  launch_vort_wall: w's frame from psi (mode PGMG_WALL_NOSLIP, walls =
+// ub, ut, vl, vr) or +0.0 (PGMG_WALL_FREE).  No span checks here (launch_extrap's rule).
+// vort_step_error / vort_wall_error: what the entries refuse in dt and nu, in the mode and the wall
+// speeds (nullptr: nothing).
+void launch_vort_step(const double *psi, long long Pp, const double *w, long long Pw, double *out,
+                      long long Po, int N, double h, double dt, double nu, double *partials,
+                      double *vmax, hipStream_t s);
+void launch_vort_wall(const double *psi, long long Pp, double *w, long long Pw, int N, double h,
+                      int mode, const double walls[4], hipStream_t s);
+const char *vort_step_error(double dt, double nu);
+const char *vort_wall_error(int mode, const double walls[4]);
+
 // --- pgmg_monitor.hip
 // the damping pass on a level of the FMG pyramid (no norm, nothing waits); fmg_damp_reserve
 // sizes the context's side buffer and partials for a level of N points beforehand

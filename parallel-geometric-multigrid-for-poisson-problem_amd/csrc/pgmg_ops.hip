@@ -18,11 +18,9 @@
 #include <string>
 #include <vector>
 
-#include "pgmg_ctx.h"
+#include "pgmg_host.h"
 
 using namespace pgmg;
-
-#define HIPC(expr) PGMG_HIPC(expr)
 
 namespace {
 
@@ -226,6 +224,65 @@ int pgmg_gradient_add_grid(const double *d_phi, long long pitch_phi, double *d_u
         return set_err(PGMG_ERR_ARG, std::string(who) + ": " + bad);
     launch_grad_update(d_phi, pitch_phi, d_u, d_v, N, gradient_weight(order, scale, h), order,
                        (hipStream_t)stream);
+    HIPC(hipGetLastError());
+    return PGMG_OK;
+}
+
+// what both vorticity ops refuse in N and h (pgmg_divergence_grid's rules)
+static int vort_op_check(const char *who, int N, double h)
+{
+    if (N < 5 || ((N - 1) & (N - 2)) != 0 || !std::isfinite(h) || h == 0.0)
+        return set_err(PGMG_ERR_ARG, std::string(who) + ": need N = 2^k + 1 with k >= 2, a finite h "
+                                                        "that is not 0");
+    return PGMG_OK;
+}
+
+// out = the explicit Euler step of omega under psi on the caller's arrays (pitch N):
+// pgmg_vorticity_step's pass (pgmg_vorticity.hip), its decomposition k_gradient's
+int pgmg_vorticity_grid(const double *d_psi, const double *d_w, double *d_out, int N, double h,
+                        double dt, double nu, double *vmax, void *stream)
+{
+    const char *const who = "pgmg_vorticity_grid";
+    int e = vort_op_check(who, N, h);
+    if (e) return e;
+    if (const char *bad = vort_step_error(dt, nu)) return set_err(PGMG_ERR_ARG, std::string(who) + ": " + bad);
+    if (!d_psi || !d_w || !d_out) return set_err(PGMG_ERR_ARG, std::string(who) + ": null psi, w or out");
+    const size_t bytes = (size_t)N * N * sizeof(double);
+    if (!device_range(d_out, N))
+        return set_err(PGMG_ERR_ARG, std::string(who) + ": out is not device memory");
+    if (ranges_overlap(d_out, bytes, d_psi, bytes) || ranges_overlap(d_out, bytes, d_w, bytes))
+        return set_err(PGMG_ERR_ARG, std::string(who) + ": out overlaps psi or w");
+    hipStream_t s = (hipStream_t)stream;
+    OpScratch *op = nullptr;
+    if ((e = ensure_scratch(s, 0, &op))) return e;
+    const size_t np = (size_t)gradient_blocks(N);
+    if (vmax && (e = ensure_grad(s, *op, np + 1))) return e;
+    double *top = vmax ? op->grad + np : nullptr;
+    launch_vort_step(d_psi, N, d_w, N, d_out, N, N, h, dt, nu, op->grad, top, s);
+    HIPC(hipGetLastError());
+    if (vmax) {
+        double t = 0.0;
+        HIPC(hipMemcpyAsync(&t, top, sizeof(t), hipMemcpyDeviceToHost, s));
+        HIPC(hipStreamSynchronize(s));
+        *vmax = t;
+    }
+    return PGMG_OK;
+}
+
+// the frame of omega from psi on the caller's arrays (pitch N): pgmg_vorticity_step's wall pass
+int pgmg_wall_vorticity_grid(const double *d_psi, double *d_w, int N, double h, int mode,
+                             const double walls[4], void *stream)
+{
+    const char *const who = "pgmg_wall_vorticity_grid";
+    int e = vort_op_check(who, N, h);
+    if (e) return e;
+    if (const char *bad = vort_wall_error(mode, walls)) return set_err(PGMG_ERR_ARG, std::string(who) + ": " + bad);
+    if (!d_psi || !d_w) return set_err(PGMG_ERR_ARG, std::string(who) + ": null psi or w");
+    const size_t bytes = (size_t)N * N * sizeof(double);
+    if (!device_range(d_w, N)) return set_err(PGMG_ERR_ARG, std::string(who) + ": w is not device memory");
+    if (ranges_overlap(d_w, bytes, d_psi, bytes))
+        return set_err(PGMG_ERR_ARG, std::string(who) + ": w overlaps psi");
+    launch_vort_wall(d_psi, N, d_w, N, N, h, mode, walls, (hipStream_t)stream);
     HIPC(hipGetLastError());
     return PGMG_OK;
 }
