@@ -1120,6 +1120,87 @@ int pgmg_correct_grid(double *d_x, const float *d_e, int N, double scale, void *
  * same stream allocates a fresh one).  Call it before destroying a stream the ops used. */
 int pgmg_ops_release(void *stream);
 
+/* ---- Batched small problems ------------------------------------------------------------------
+ * Every entry above solves one problem per context, and the host steers each solve: at N <= 65 a
+ * cycle is one launch of one workgroup, and a solve waits for a residual norm before every chunk of
+ * cycles.  The batch entries run B independent problems of the same size N <= 65 in ONE launch,
+ * one workgroup per problem: workgroup b loads problem b into LDS, cycles it there with the code of
+ * the contexts' one-workgroup tail, in pgmg_batch_solve decides convergence by itself, and stores
+ * phi.  No context, no host round trip inside the launch, nothing shared between the problems.
+ *
+ * Arrays.  d_phi and d_f are device arrays of B * N * N elements, problem b at element b * N * N
+ * in the reference layout (pitch N): double for PGMG_PRECISION_FP64, float for _FP32 (unlike a
+ * context's ABI, an fp32 batch reads and writes floats).  phi is updated in place, frame included
+ * (the frame is the problem's Dirichlet data and is stored back bit for bit); f is only read.
+ * Asynchronous on `stream` (a hipStream_t; NULL: the default stream), like the op-level entries.
+ *
+ * pgmg_batch_cycle: `ncycles` V-cycles (PGMG_CYCLE_V) or W-cycles with cfg->alpha visits
+ * (PGMG_CYCLE_W) of every problem: bit for bit what pgmg_vcycle / pgmg_wcycle do to that problem on
+ * a context of the same N, v1, v2, coarse_iter, n_coarse, alpha, eps, precision and h0 = h.
+ * d_sweeps / d_exits (each may be NULL): B words, the problem's own sweeps and early exits, what
+ * pgmg_stats counts for it.
+ *
+ * pgmg_batch_solve: per problem, pgmg_solve_damped's loop and stop rule (above: "Convergence
+ * monitor and solve-to-tolerance", "Damping pass and damped solve") restated on the device.  At
+ * check i, after k_i cycles:
+ *   1. r_i = sqrt(sum over the interior of r^2), r = f - ih (4x - x_l - x_r - x_u - x_d) in the
+ *      element type (pgmg_monitor's expression), squared and summed in double in a fixed order
+ *      (a thread's points in index order, then lanes, then waves).  The bits are a function of
+ *      (phi, f, N, h) alone: not of B, of the problem's index or of where the workgroup ran.  Only
+ *      the summation order differs from the sequential sum: within N^2 2^-52 relative of it.
+ *   2. omega > 0: x <- x + w r on the interior, w = (T)(omega * 0.25 * (h * h)), every r from the
+ *      x of before the update, two roundings, no fused multiply-add, the frame never written:
+ *      pgmg_damp's formula.  omega == 0: nothing is written, the loop is plain pgmg_solve's.
+ *   3. pgmg_solve's rule in its order: r_i not finite -> PGMG_STOP_NONFINITE; r_i <= max(atol,
+ *      rtol * r_0) -> _CONVERGED; the stall streak -> _STALLED; k_i >= max_cycles -> _MAX_CYCLES.
+ *   4. otherwise min(check_every, max_cycles - k_i) cycles of opts->cycle, and the next check.
+ * As in pgmg_solve_damped the stopping check's correction is applied.  Problems stop
+ * independently; a problem whose data holds a NaN ends with PGMG_STOP_NONFINITE at check 0 and
+ * touches nothing of its neighbours.  Tolerances are shared by the batch (state atol in the units
+ * of the f's at hand).  opts->monitor is ignored apart from the PGMG_MON_ERROR refusal below.
+ * out (may be NULL, as may any of its arrays): device arrays of B entries written by the launch --
+ * cycles, checks, reason, res0 (r_0), res (the last r_i), sweeps, exits; history: B x history_cap
+ * norms, check 0 first, slots past the problem's last check (and checks past history_cap: not
+ * recorded) NaN.  Read them after the stream has finished.
+ *
+ * pgmg_batch_time (measurement): B problems of pseudo-random right-hand sides in arrays of its
+ * own, `reps` launches of pgmg_batch_cycle(cycle, ncycles) back to back on the default stream
+ * between two hipEvents after two warm ones; mean device ms per launch.  Synchronous.
+ *
+ * Sizes.  N = 65 in fp64 takes 122 KiB of a CU's 160 KiB of LDS, and at every N the kernel's
+ * registers allow one workgroup per CU: a batch runs min(B, CUs) problems at a time and its time
+ * grows in steps of that many problems.
+ *
+ * PGMG_ERR_ARG, before any HIP call: a null cfg, opts, phi or f; B < 1 (or above 2^31 - 1); N
+ * other than 5, 9, 17, 33, 65; v1, v2, coarse_iter, n_coarse, alpha outside pgmg_create's bounds;
+ * h zero or not finite (negative is legal); an unknown precision; omega not finite or outside
+ * [0, 1]; options pgmg_solve refuses; PGMG_CYCLE_F (it rebuilds the analytic f); PGMG_MON_ERROR;
+ * ncycles < 0; history_cap < 0.  The model is tests/batch_model.py. */
+typedef struct pgmg_batch_config {
+    int N;                      /* 5, 9, 17, 33 or 65 */
+    int v1, v2, coarse_iter, n_coarse, alpha;   /* pgmg_config's meaning, defaults and bounds */
+    double eps;                 /* smoother early exit; < 0: never */
+    double h;                   /* mesh width, finite and not 0; default 1 / (N - 1) */
+    int precision;              /* PGMG_PRECISION_FP64: double arrays; _FP32: float arrays */
+} pgmg_batch_config;
+int pgmg_batch_config_default(pgmg_batch_config *cfg, int N);
+
+typedef struct pgmg_batch_out {         /* device arrays of B entries each; any may be NULL */
+    int *cycles, *checks, *reason;      /* PGMG_STOP_* */
+    double *res0, *res;
+    long long *sweeps, *exits;          /* what pgmg_stats counts, per problem */
+    double *history; int history_cap;   /* B x history_cap norms, check 0 first; unused slots NaN */
+} pgmg_batch_out;
+
+int pgmg_batch_cycle(const pgmg_batch_config *cfg, int cycle /* PGMG_CYCLE_V | _W */, int ncycles,
+                     void *d_phi, const void *d_f, long long B,
+                     long long *d_sweeps, long long *d_exits, void *stream);
+int pgmg_batch_solve(const pgmg_batch_config *cfg, const pgmg_solve_opts *o, double omega,
+                     void *d_phi, const void *d_f, long long B,
+                     const pgmg_batch_out *out, void *stream);
+int pgmg_batch_time(const pgmg_batch_config *cfg, int cycle, int ncycles, long long B, int reps,
+                    double *ms_per_launch);   /* own scratch arrays, two warm launches, hipEvents */
+
 /* ---- device memory helpers (for host code built without HIP headers) ----- */
 int pgmg_device_alloc(void **ptr, size_t bytes);
 int pgmg_device_free(void *ptr);

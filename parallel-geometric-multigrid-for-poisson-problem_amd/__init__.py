@@ -34,7 +34,7 @@ from ._capi import (PGMG_FLAG_LOOPBACK, PGMG_FLAG_NO_CROSS, PGMG_FLAG_NO_GRAPH,
 PKG_DIR = pathlib.Path(__file__).resolve().parent
 
 __all__ = [
-    "build", "load", "Solver", "PgmgConfig", "PgmgError", "ops", "config_overrides",
+    "build", "load", "Solver", "BatchSolver", "PgmgConfig", "PgmgError", "ops", "config_overrides",
     "PGMG_FLAG_NO_GRAPH", "PGMG_FLAG_TIME_FINE", "PGMG_FLAG_UNFUSED", "PGMG_FLAG_LOOPBACK", "PGMG_FLAG_NO_CROSS",
     "PGMG_PROLONG_REFERENCE", "plan_strips", "LoopbackHub", "unique_id", "rccl_latency",
     "PGMG_PROLONG_SYMMETRIC", "PGMG_PRECISION_FP64", "PGMG_PRECISION_FP32",
@@ -703,6 +703,125 @@ class Solver:
         m = C.c_double()
         check(self.lib.pgmg_bench_sweep(self.h, int(reps), C.byref(m)), "pgmg_bench_sweep")
         return m.value
+
+
+class BatchSolver:
+    """Many independent Poisson problems of one size N <= 65 in one launch, one workgroup each
+    (include/pgmg.h "Batched small problems").  No context: only the configuration is kept.
+
+        bs = BatchSolver(33)                       # v1, v2, coarse_iter, n_coarse, alpha, eps, h
+        out = bs.solve(phi, f, atol=1e-8, rtol=0)  # phi, f: [B, N, N] CUDA tensors, phi in place
+        torch.cuda.synchronize(); out.cycles       # per-problem results, device tensors
+
+    dtype "f64" takes float64 tensors, "f32" float32 ones."""
+
+    def __init__(self, N, dtype="f64", **cfg):
+        from ._capi import PgmgBatchConfig
+        self.lib = load()
+        if dtype not in ("f64", "f32"):
+            raise ValueError(f"dtype must be 'f64' or 'f32', not {dtype!r}")
+        self.dtype = dtype
+        self.N = int(N)
+        self.cfg = PgmgBatchConfig()
+        check(self.lib.pgmg_batch_config_default(C.byref(self.cfg), self.N),
+              "pgmg_batch_config_default")
+        self.cfg.precision = PGMG_PRECISION_FP32 if dtype == "f32" else PGMG_PRECISION_FP64
+        for k, v in cfg.items():
+            if not hasattr(self.cfg, k):
+                raise TypeError(f"unknown batch config field {k}")
+            setattr(self.cfg, k, v)
+
+    def _arrays(self, phi, f):
+        """B of a matching pair of [B, N, N] device tensors; PgmgError otherwise."""
+        import torch
+        want = torch.float32 if self.dtype == "f32" else torch.float64
+        for name, t in (("phi", phi), ("f", f)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise PgmgError(f"BatchSolver: {name} must be a CUDA tensor")
+            if t.dtype != want:
+                raise PgmgError(f"BatchSolver: {name} must be {want}, not {t.dtype}")
+            if t.dim() != 3 or tuple(t.shape[1:]) != (self.N, self.N) or t.shape[0] < 1:
+                raise PgmgError(f"BatchSolver: {name} must have shape [B, {self.N}, {self.N}], "
+                                f"not {tuple(t.shape)}")
+            if not t.is_contiguous():
+                raise PgmgError(f"BatchSolver: {name} must be contiguous")
+        if phi.shape[0] != f.shape[0] or phi.device != f.device:
+            raise PgmgError("BatchSolver: phi and f must hold the same number of problems on one device")
+        return int(phi.shape[0])
+
+    @staticmethod
+    def _stream(t):
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+    @staticmethod
+    def _kind(kind):
+        kinds = {"V": PGMG_CYCLE_V, "W": PGMG_CYCLE_W, "F": PGMG_CYCLE_F}
+        return kinds[kind] if kind in kinds else int(kind)
+
+    def cycle(self, phi, f, n=1, kind="V", stats=False):
+        """`n` V- or W-cycles of every problem, in place in phi, asynchronous on torch's current
+        stream (pgmg_batch_cycle).  stats=True: returns (sweeps, exits), int64 device tensors of B
+        entries, each problem's own counts."""
+        import torch
+        B = self._arrays(phi, f)
+        sw = ex = None
+        if stats:
+            sw = torch.empty(B, dtype=torch.int64, device=phi.device)
+            ex = torch.empty(B, dtype=torch.int64, device=phi.device)
+        with torch.cuda.device(phi.device):
+            check(self.lib.pgmg_batch_cycle(C.byref(self.cfg), self._kind(kind), int(n), _dptr(phi),
+                                            _dptr(f), B, _dptr(sw), _dptr(ex), self._stream(phi)),
+                  "pgmg_batch_cycle")
+        return (sw, ex) if stats else None
+
+    def solve(self, phi, f, rtol=1e-3, atol=0.0, max_cycles=30, check_every=1, damp=0.5,
+              stall_ratio=0.0, stall_checks=2, kind="V", history=False):
+        """Solve every problem to max(atol, rtol * r0) by pgmg_solve_damped's loop, each workgroup
+        deciding for its own problem (pgmg_batch_solve); damp=0 is the plain solve.  Asynchronous
+        on torch's current stream: returns a namespace of device tensors of B entries -- cycles,
+        checks, reason (int32), res0, res (float64), sweeps, exits (int64) and, with history=True,
+        history [B, max_cycles + 1] (float64, check 0 first, unused slots NaN) -- valid once the
+        stream has finished (it does not synchronise)."""
+        import torch
+        from types import SimpleNamespace
+        from ._capi import PgmgBatchOut
+        B = self._arrays(phi, f)
+        dev = phi.device
+        o = PgmgSolveOpts()
+        check(self.lib.pgmg_solve_opts_default(C.byref(o)), "pgmg_solve_opts_default")
+        o.cycle = self._kind(kind)
+        o.rtol, o.atol, o.max_cycles, o.check_every = rtol, atol, int(max_cycles), int(check_every)
+        o.stall_ratio, o.stall_checks = stall_ratio, int(stall_checks)
+        o.monitor = PGMG_MON_RESIDUAL
+        res = SimpleNamespace(
+            cycles=torch.empty(B, dtype=torch.int32, device=dev),
+            checks=torch.empty(B, dtype=torch.int32, device=dev),
+            reason=torch.empty(B, dtype=torch.int32, device=dev),
+            res0=torch.empty(B, dtype=torch.float64, device=dev),
+            res=torch.empty(B, dtype=torch.float64, device=dev),
+            sweeps=torch.empty(B, dtype=torch.int64, device=dev),
+            exits=torch.empty(B, dtype=torch.int64, device=dev))
+        out = PgmgBatchOut()
+        for name in ("cycles", "checks", "reason", "res0", "res", "sweeps", "exits"):
+            setattr(out, name, getattr(res, name).data_ptr())
+        if history:
+            cap = max(int(max_cycles), 0) + 1
+            res.history = torch.empty((B, cap), dtype=torch.float64, device=dev)
+            out.history, out.history_cap = res.history.data_ptr(), cap
+        with torch.cuda.device(dev):
+            check(self.lib.pgmg_batch_solve(C.byref(self.cfg), C.byref(o), float(damp), _dptr(phi),
+                                            _dptr(f), B, C.byref(out), self._stream(phi)),
+                  "pgmg_batch_solve")
+        return res
+
+    def time(self, B, n=1, kind="V", reps=20):
+        """Mean device ms of one launch of `n` cycles on B problems of pseudo-random right-hand
+        sides in the library's own arrays (pgmg_batch_time; measurement, synchronous)."""
+        ms = C.c_double()
+        check(self.lib.pgmg_batch_time(C.byref(self.cfg), self._kind(kind), int(n), int(B),
+                                       int(reps), C.byref(ms)), "pgmg_batch_time")
+        return ms.value
 
 
 def _dptr(t):

@@ -141,6 +141,18 @@ class PgmgMixedInfo(C.Structure):
                 ("elapsed_ms", C.c_double)]
 
 
+class PgmgBatchConfig(C.Structure):
+    _fields_ = [("N", C.c_int), ("v1", C.c_int), ("v2", C.c_int), ("coarse_iter", C.c_int),
+                ("n_coarse", C.c_int), ("alpha", C.c_int), ("eps", C.c_double), ("h", C.c_double),
+                ("precision", C.c_int)]
+
+
+class PgmgBatchOut(C.Structure):
+    _fields_ = [("cycles", C.c_void_p), ("checks", C.c_void_p), ("reason", C.c_void_p),
+                ("res0", C.c_void_p), ("res", C.c_void_p), ("sweeps", C.c_void_p),
+                ("exits", C.c_void_p), ("history", C.c_void_p), ("history_cap", C.c_int)]
+
+
 # (name, restype, argtypes) for every symbol include/pgmg.h declares
 _P = C.c_void_p
 _DP = C.POINTER(C.c_double)
@@ -238,6 +250,13 @@ SIGNATURES = [
                                       _P]),
     ("pgmg_wall_vorticity_grid", C.c_int, [_P, _P, C.c_int, C.c_double, C.c_int, _DP, _P]),
     ("pgmg_ops_release", C.c_int, [_P]),
+    ("pgmg_batch_config_default", C.c_int, [C.POINTER(PgmgBatchConfig), C.c_int]),
+    ("pgmg_batch_cycle", C.c_int, [C.POINTER(PgmgBatchConfig), C.c_int, C.c_int, _P, _P,
+                                   C.c_longlong, _P, _P, _P]),
+    ("pgmg_batch_solve", C.c_int, [C.POINTER(PgmgBatchConfig), C.POINTER(PgmgSolveOpts), C.c_double,
+                                   _P, _P, C.c_longlong, C.POINTER(PgmgBatchOut), _P]),
+    ("pgmg_batch_time", C.c_int, [C.POINTER(PgmgBatchConfig), C.c_int, C.c_int, C.c_longlong,
+                                  C.c_int, _DP]),
     ("pgmg_device_alloc", C.c_int, [C.POINTER(_P), C.c_size_t]),
     ("pgmg_device_free", C.c_int, [_P]),
     ("pgmg_memcpy_h2d", C.c_int, [_P, _P, C.c_size_t]),
