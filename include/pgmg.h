@@ -831,6 +831,83 @@ int pgmg_vorticity_step(pgmg_ctx *ctx, const pgmg_solve_opts *o, double omega, d
                         int mode, const double walls[4], int nsteps, pgmg_vort_info *info);
 int pgmg_vorticity_time(pgmg_ctx *ctx, int which, int reps, double *ms_per_pass, double *bytes);
 
+/* ---- Buoyancy-driven flow ---------------------------------------------------------------------
+ * pgmg_boussinesq_step(ctx, opts, omega, p, d_T, nsteps, info): the flow of "Vorticity transport"
+ * above carrying a scalar T (a temperature) that feeds back into the vorticity equation, the
+ * Boussinesq approximation:
+ *     w_t + u w_x + v w_y = nu lap(w) + (by T_x - bx T_y)
+ *     T_t + u T_x + v T_y = kappa lap(T)
+ *     -lap(psi) = w,    u = psi_y,    v = -psi_x
+ * (gravity along -y: bx = 0, by = g beta).  The state (psi, w) is the context's problem (phi, f),
+ * as for pgmg_vorticity_step; d_T is the caller's device array, N x N doubles at pitch N, updated
+ * in place.  Every convention is that section's: fp64, one GPU, context-owned problems,
+ * synchronous; element (j, i) at x = i h, y = j h; h the context's finest mesh width (a negative h
+ * is used as written); expressions evaluated left to right as written, one rounding per
+ * operation, no fused multiply-add.  P is psi, W is w.
+ *   The step, on the interior 1 <= y, x <= N - 2, with wgt = 0.5 / h and ih = 1.0 / (h * h); px,
+ *   py, wx, wy and lapw are "Vorticity transport"'s px, py, wx, wy and lap:
+ *     tx   = (T[y][x+1] - T[y][x-1]) * wgt        ty = (T[y+1][x] - T[y-1][x]) * wgt
+ *     advw = py * wx - px * wy                     advt = py * tx - px * ty
+ *     lapt = (T[y][x-1] + T[y][x+1] + T[y-1][x] + T[y+1][x] - 4.0 * T[y][x]) * ih
+ *     src  = by * tx - bx * ty                     two products, one subtraction
+ *     Wout[y][x] = W[y][x] + dt * ((nu * lapw - advw) + src)
+ *     Tout[y][x] = T[y][x] + dt * (kappa * lapt - advt)
+ *   Every term comes from the P, W and T of before the pass, which is one launch: 24 B read and
+ *   16 B written per point.  The frame of Wout is W's frame and the frame of Tout is T's, word for
+ *   word (a -0.0 stays -0.0; Dirichlet temperatures are simply never written).  vmax is
+ *   "Vorticity transport"'s.  So Tout is bit for bit that section's step of T under P with kappa
+ *   for nu, and with bx = by = 0 and finite inputs Wout equals its step of W as numbers (the
+ *   added +0.0 can change the sign of a zero and nothing else).
+ *   The scalar wall pass, on the frame of T: each bit of `adiabatic` makes its wall adiabatic by
+ *   the second-order one-sided dT/dn = 0, written so that a constant field is kept exactly; K3 is
+ *   the double nearest 1/3 (0x3FD5555555555555; a product, not a division):
+ *     PGMG_TWALL_BOTTOM  T[0][x]   = T[1][x]   + (T[1][x]   - T[2][x])   * K3      1 <= x <= N - 2
+ *     PGMG_TWALL_TOP     T[N-1][x] = T[N-2][x] + (T[N-2][x] - T[N-3][x]) * K3
+ *     PGMG_TWALL_LEFT    T[y][0]   = T[y][1]   + (T[y][1]   - T[y][2])   * K3      1 <= y <= N - 2
+ *     PGMG_TWALL_RIGHT   T[y][N-1] = T[y][N-2] + (T[y][N-2] - T[y][N-3]) * K3
+ *   A wall whose bit is clear is Dirichlet and is not touched; the four corners are never written
+ *   (no interior stencil reads them); mask 0 writes nothing.  Every value read is an interior
+ *   value, so the four walls do not depend on each other.
+ * Per step:
+ *   1. The wall passes: "Vorticity transport"'s on f's frame from the current phi (p->mode,
+ *      p->walls), and the scalar wall pass on d_T's frame.
+ *   2. The step, phi, f and d_T read where they lie, into two scratch grids (f's for w, as
+ *      pgmg_vorticity_step's; a context-owned N x N grid for T, allocated on the first call) that
+ *      are then copied on the stream onto f and onto d_T.  The context's problem is then one with
+ *      a caller's f, exactly as step 2 of pgmg_vorticity_step leaves it.
+ *   3. pgmg_solve_damped(ctx, opts, omega, &info->flow.last), warm-started from the previous psi.
+ * After the last step both wall passes run once more: nsteps = 3 gives the bits of three calls of
+ * one step.  info->flow is filled as pgmg_vorticity_step fills its info (cfl from the last step's
+ * vmax, diffusion = 4 nu dt / h^2); diffusion_t = 4 kappa dt / h^2.  Stability is the caller's
+ * business: cfl, diffusion and diffusion_t at most about 1.  The scheme is first order in time
+ * and second order in space.  The model is tests/bouss_model.py.
+ * Errors, all before anything is written.  PGMG_ERR_ARG: everything pgmg_vorticity_step refuses
+ * (dt, nu, mode and walls read from p); a null p or d_T; a d_T that is not device memory; kappa
+ * not finite or < 0; a buoy component that is not finite; an adiabatic bit above 8.
+ * PGMG_ERR_STATE: before pgmg_set_problem; world > 1; an fp32 context; a device-bound problem.
+ * pgmg_boussinesq_time: pgmg_vorticity_time's measurement on five context-owned scratch arrays
+ * allocated on the first call (40 N^2 bytes): which = 0 the step with both copies back (72 N^2
+ * bytes), which = 1 the step with vmax, both launches (40 N^2).  Neither phi, f nor any caller
+ * array is written. */
+#define PGMG_TWALL_BOTTOM 1u
+#define PGMG_TWALL_TOP 2u
+#define PGMG_TWALL_LEFT 4u
+#define PGMG_TWALL_RIGHT 8u
+typedef struct pgmg_bouss_params {
+    double dt, nu, kappa;
+    double buoy[2];        /* bx, by: w_t += by T_x - bx T_y (gravity along -y: bx = 0, by = g beta) */
+    int mode;              /* PGMG_WALL_NOSLIP | PGMG_WALL_FREE */
+    double walls[4];       /* ub, ut, vl, vr as in pgmg_vorticity_step */
+    unsigned adiabatic;    /* PGMG_TWALL_* */
+} pgmg_bouss_params;
+typedef struct pgmg_bouss_info {
+    pgmg_vort_info flow;   /* as pgmg_vorticity_step fills it */
+    double diffusion_t;    /* 4 * kappa * dt / (h * h) */
+} pgmg_bouss_info;
+int pgmg_boussinesq_step(pgmg_ctx *ctx, const pgmg_solve_opts *o, double omega,
+                         const pgmg_bouss_params *p, double *d_T, int nsteps, pgmg_bouss_info *info);
+int pgmg_boussinesq_time(pgmg_ctx *ctx, int which, int reps, double *ms_per_pass, double *bytes);
+
 /* ---- Mixed-precision refinement ----------------------------------------------------------
  * pgmg_solve_mixed(ctx, opts, nu, omega, info): fp64 solutions from fp32 multigrid corrections
  * (defect correction).  The iterate phi and its residual stay in fp64 on the fp64 context ctx,
@@ -1101,6 +1178,20 @@ int pgmg_vorticity_grid(const double *d_psi, const double *d_w, double *d_out, i
                         double dt, double nu, double *vmax, void *stream);
 int pgmg_wall_vorticity_grid(const double *d_psi, double *d_w, int N, double h, int mode,
                              const double walls[4], void *stream);
+/* The two passes of pgmg_boussinesq_step ("Buoyancy-driven flow" above) on caller-owned device
+ * arrays of doubles at pitch N, N = 2^k + 1 with k >= 2, under the contract of the two entries
+ * above.
+ * pgmg_boussinesq_grid: d_wout and d_Tout = the steps of d_w and d_T under d_psi on the interior,
+ * their frames on the frame; d_psi, d_w and d_T are only read; an output must not overlap an
+ * input or the other output.  vmax == NULL: asynchronous on `stream`; otherwise synchronous.
+ * pgmg_wall_scalar_grid: the scalar wall pass in place on d_T's frame; adiabatic = a mask of
+ * PGMG_TWALL_*.  Asynchronous on `stream`.
+ * The argument errors of the two entries above, kappa not finite or < 0, a null or non-finite
+ * buoy, an adiabatic bit above 8: PGMG_ERR_ARG, nothing enqueued. */
+int pgmg_boussinesq_grid(const double *d_psi, const double *d_w, const double *d_T, double *d_wout,
+                         double *d_Tout, int N, double h, double dt, double nu, double kappa,
+                         const double buoy[2], double *vmax, void *stream);
+int pgmg_wall_scalar_grid(double *d_T, int N, unsigned adiabatic, void *stream);
 /* The two passes of pgmg_solve_mixed ("Mixed-precision refinement" above) on caller-owned device
  * arrays at pitch N, N = 2^k + 1 with k >= 2: x and f fp64, g and e fp32.
  * pgmg_defect_grid: g = (float)(r * scale) on the interior, +0.0f on the frame, r the fp64 residual

@@ -29,7 +29,8 @@ from ._capi import (PGMG_FLAG_LOOPBACK, PGMG_FLAG_NO_CROSS, PGMG_FLAG_NO_GRAPH,
                     PGMG_STOP_CONVERGED, PGMG_STOP_MAX_CYCLES, PGMG_STOP_STALLED,
                     PGMG_STOP_NONFINITE, PgmgMonitorOut, PgmgSolveOpts, PgmgSolveInfo,
                     PgmgExtrapInfo, PgmgProjectInfo, PgmgMixedInfo, PgmgVortInfo,
-                    PGMG_WALL_NOSLIP, PGMG_WALL_FREE, check, load)
+                    PGMG_WALL_NOSLIP, PGMG_WALL_FREE, PgmgBoussParams, PgmgBoussInfo,
+                    PGMG_TWALL_BOTTOM, PGMG_TWALL_TOP, PGMG_TWALL_LEFT, PGMG_TWALL_RIGHT, check, load)
 
 PKG_DIR = pathlib.Path(__file__).resolve().parent
 
@@ -45,7 +46,29 @@ __all__ = [
     "PGMG_STOP_CONVERGED", "PGMG_STOP_MAX_CYCLES", "PGMG_STOP_STALLED", "PGMG_STOP_NONFINITE",
     "PgmgSolveOpts", "PgmgSolveInfo", "PgmgMonitorOut", "PgmgExtrapInfo",
     "PgmgProjectInfo", "PgmgMixedInfo", "PgmgVortInfo", "PGMG_WALL_NOSLIP", "PGMG_WALL_FREE",
+    "PgmgBoussParams", "PgmgBoussInfo", "PGMG_TWALL_BOTTOM", "PGMG_TWALL_TOP", "PGMG_TWALL_LEFT",
+    "PGMG_TWALL_RIGHT", "twall_mask",
 ]
+
+_TWALLS = {"bottom": PGMG_TWALL_BOTTOM, "top": PGMG_TWALL_TOP, "left": PGMG_TWALL_LEFT,
+           "right": PGMG_TWALL_RIGHT}
+
+
+def twall_mask(adiabatic):
+    """The PGMG_TWALL_* mask of `adiabatic`: an int is taken as the mask itself, otherwise the
+    names of the adiabatic walls among "bottom" (y = 0), "top", "left" (x = 0) and "right"."""
+    if isinstance(adiabatic, int):
+        if not 0 <= adiabatic < 2 ** 32:
+            raise ValueError("adiabatic: a mask is an unsigned 32-bit value")
+        return adiabatic
+    if isinstance(adiabatic, str):
+        adiabatic = (adiabatic,)
+    mask = 0
+    for name in adiabatic:
+        if name not in _TWALLS:
+            raise ValueError(f"adiabatic: {name!r} is none of {sorted(_TWALLS)}")
+        mask |= _TWALLS[name]
+    return mask
 
 
 def build(jobs=8, verbose=False):
@@ -506,6 +529,52 @@ class Solver:
         ms, b = C.c_double(), C.c_double()
         check(self.lib.pgmg_vorticity_time(self.h, int(which), int(reps), C.byref(ms), C.byref(b)),
               "pgmg_vorticity_time")
+        return ms.value, b.value
+
+    def boussinesq_step(self, T, dt, nu, kappa, buoy=(0.0, 1.0), walls=(0.0, 0.0, 0.0, 0.0),
+                        free=False, adiabatic=("bottom", "top"), nsteps=1, damp=0.5, atol=0.0,
+                        rtol=0.0, max_cycles=30, check_every=1):
+        """`nsteps` explicit Euler steps of buoyancy-driven flow (pgmg_boussinesq_step):
+        vorticity_step's flow carrying the temperature T, which feeds back into the vorticity:
+        f_t + u f_x + v f_y = nu lap(f) + (by T_x - bx T_y), T_t + u T_x + v T_y = kappa lap(T),
+        buoy = (bx, by) (gravity along -y: (0, g beta)).  T: a contiguous N x N float64 CUDA
+        tensor, updated in place; its walls named in `adiabatic` ("bottom", "top", "left", "right",
+        or a PGMG_TWALL_* mask) are set by the one-sided dT/dn = 0 before every step and after the
+        last, the others keep the values T came with (Dirichlet).  Both steps are one pass over
+        psi, f and T.  walls, free and the solve's arguments are vorticity_step's.  Returns its
+        namespace plus diffusion_t = 4 kappa dt / h^2 (keep it at most 1).  fp64, one GPU,
+        context-owned problems."""
+        import torch
+        from types import SimpleNamespace
+        N = self.N
+        if not (isinstance(T, torch.Tensor) and T.is_cuda and T.dtype == torch.float64
+                and tuple(T.shape) == (N, N) and T.is_contiguous()):
+            raise ValueError("T must be a contiguous N x N float64 CUDA tensor")
+        o = PgmgSolveOpts()
+        check(self.lib.pgmg_solve_opts_default(C.byref(o)), "pgmg_solve_opts_default")
+        o.rtol, o.atol, o.max_cycles, o.check_every = rtol, atol, int(max_cycles), int(check_every)
+        p = PgmgBoussParams()
+        p.dt, p.nu, p.kappa = float(dt), float(nu), float(kappa)
+        p.buoy = (C.c_double * 2)(*(float(x) for x in buoy))
+        p.mode = PGMG_WALL_FREE if free else PGMG_WALL_NOSLIP
+        p.walls = (C.c_double * 4)(*(float(x) for x in walls))
+        p.adiabatic = twall_mask(adiabatic)
+        info = PgmgBoussInfo()
+        check(self.lib.pgmg_boussinesq_step(self.h, C.byref(o), float(damp), C.byref(p), _dptr(T),
+                                            int(nsteps), C.byref(info)), "pgmg_boussinesq_step")
+        out = SimpleNamespace(**{name: getattr(info.flow, name) for name, _ in PgmgVortInfo._fields_})
+        out.diffusion_t = info.diffusion_t
+        out.history = self.history()
+        return out
+
+    def boussinesq_time(self, which, reps=20):
+        """(mean device ms, algorithmic bytes) of one pass of boussinesq_step over `reps` back to
+        back on context-owned arrays (pgmg_boussinesq_time; measurement): which=0 the step with
+        both copies back, which=1 the step with the velocity maximum.  Leaves phi, f and every
+        caller's array alone."""
+        ms, b = C.c_double(), C.c_double()
+        check(self.lib.pgmg_boussinesq_time(self.h, int(which), int(reps), C.byref(ms), C.byref(b)),
+              "pgmg_boussinesq_time")
         return ms.value, b.value
 
     def velocity(self, u=None, v=None):
@@ -1039,6 +1108,35 @@ class _Ops:
                                               PGMG_WALL_FREE if free else PGMG_WALL_NOSLIP, ws,
                                               stream), "pgmg_wall_vorticity_grid")
         return w
+
+    def boussinesq_step(self, psi, w, T, w_out, T_out, h, dt, nu, kappa, buoy, vmax=False, stream=None):
+        """w_out = w + dt ((nu lap(w) - (psi_y w_x - psi_x w_y)) + (by T_x - bx T_y)) and T_out = T
+        + dt (kappa lap(T) - (psi_y T_x - psi_x T_y)) on the interior, the frames of w and T on the
+        frames, in one pass (pgmg_boussinesq_grid): N x N float64 device arrays, N = 2^k + 1,
+        k >= 2; h finite and not 0; buoy = (bx, by); an output must not overlap an input or the
+        other output.  vmax=False: returns (w_out, T_out), asynchronous on `stream`; vmax=True:
+        returns (w_out, T_out, max |psi_x| + |psi_y| over the interior), synchronous."""
+        N = psi.shape[0]
+        for t in (psi, w, T, w_out, T_out):
+            assert tuple(t.shape) == (N, N), t.shape
+        m = C.c_double()
+        b = (C.c_double * 2)(*(float(x) for x in buoy))
+        check(load().pgmg_boussinesq_grid(self._ptr(psi), self._ptr(w), self._ptr(T),
+                                          self._ptr(w_out), self._ptr(T_out), N, float(h), float(dt),
+                                          float(nu), float(kappa), b, C.byref(m) if vmax else None,
+                                          stream), "pgmg_boussinesq_grid")
+        return (w_out, T_out, m.value) if vmax else (w_out, T_out)
+
+    def wall_scalar(self, T, adiabatic, stream=None):
+        """The adiabatic walls of T by the second-order one-sided dT/dn = 0, in place
+        (pgmg_wall_scalar_grid): adiabatic names the walls ("bottom", "top", "left", "right") or is
+        a PGMG_TWALL_* mask; the other walls and the four corners keep their values.  Asynchronous
+        on `stream`."""
+        N = T.shape[0]
+        assert tuple(T.shape) == (N, N), T.shape
+        check(load().pgmg_wall_scalar_grid(self._ptr(T), N, twall_mask(adiabatic), stream),
+              "pgmg_wall_scalar_grid")
+        return T
 
     def release(self, stream=None):
         """Wait for `stream` and free the scratch set the ops keep for it (pgmg_ops_release)."""

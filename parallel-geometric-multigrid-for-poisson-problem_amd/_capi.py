@@ -58,6 +58,10 @@ PGMG_STOP_STALLED = 3
 PGMG_STOP_NONFINITE = 4
 PGMG_WALL_NOSLIP = 0
 PGMG_WALL_FREE = 1
+PGMG_TWALL_BOTTOM = 1
+PGMG_TWALL_TOP = 2
+PGMG_TWALL_LEFT = 4
+PGMG_TWALL_RIGHT = 8
 
 
 # pgmg_host_transport (include/pgmg.h): the caller's message functions
@@ -135,6 +139,16 @@ class PgmgVortInfo(C.Structure):
                 ("solve_ms", C.c_double), ("elapsed_ms", C.c_double)]
 
 
+class PgmgBoussParams(C.Structure):
+    _fields_ = [("dt", C.c_double), ("nu", C.c_double), ("kappa", C.c_double),
+                ("buoy", C.c_double * 2), ("mode", C.c_int), ("walls", C.c_double * 4),
+                ("adiabatic", C.c_uint)]
+
+
+class PgmgBoussInfo(C.Structure):
+    _fields_ = [("flow", PgmgVortInfo), ("diffusion_t", C.c_double)]
+
+
 class PgmgMixedInfo(C.Structure):
     _fields_ = [("solve", PgmgSolveInfo), ("inner_sweeps", C.c_longlong),
                 ("defect_ms", C.c_double), ("inner_ms", C.c_double), ("correct_ms", C.c_double),
@@ -199,6 +213,10 @@ SIGNATURES = [
     ("pgmg_vorticity_step", C.c_int, [_P, C.POINTER(PgmgSolveOpts), C.c_double, C.c_double,
                                       C.c_double, C.c_int, _DP, C.c_int, C.POINTER(PgmgVortInfo)]),
     ("pgmg_vorticity_time", C.c_int, [_P, C.c_int, C.c_int, _DP, _DP]),
+    ("pgmg_boussinesq_step", C.c_int, [_P, C.POINTER(PgmgSolveOpts), C.c_double,
+                                       C.POINTER(PgmgBoussParams), _P, C.c_int,
+                                       C.POINTER(PgmgBoussInfo)]),
+    ("pgmg_boussinesq_time", C.c_int, [_P, C.c_int, C.c_int, _DP, _DP]),
     ("pgmg_solve_mixed", C.c_int, [_P, C.POINTER(PgmgSolveOpts), C.c_int, C.c_double,
                                    C.POINTER(PgmgMixedInfo)]),
     ("pgmg_mixed_time", C.c_int, [_P, C.c_int, C.c_int, _DP, _DP]),
@@ -249,6 +267,9 @@ SIGNATURES = [
     ("pgmg_vorticity_grid", C.c_int, [_P, _P, _P, C.c_int, C.c_double, C.c_double, C.c_double, _DP,
                                       _P]),
     ("pgmg_wall_vorticity_grid", C.c_int, [_P, _P, C.c_int, C.c_double, C.c_int, _DP, _P]),
+    ("pgmg_boussinesq_grid", C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_double, C.c_double,
+                                       C.c_double, C.c_double, _DP, _DP, _P]),
+    ("pgmg_wall_scalar_grid", C.c_int, [_P, C.c_int, C.c_uint, _P]),
     ("pgmg_ops_release", C.c_int, [_P]),
     ("pgmg_batch_config_default", C.c_int, [C.POINTER(PgmgBatchConfig), C.c_int]),
     ("pgmg_batch_cycle", C.c_int, [C.POINTER(PgmgBatchConfig), C.c_int, C.c_int, _P, _P,

@@ -286,6 +286,11 @@ struct pgmg_ctx {
     pgmg::Grid vt_out;
     hipEvent_t vt_ev[2] = {};
     double *vt_scr = nullptr;
+    // pgmg_boussinesq_step (pgmg_boussinesq.hip), made on the first call that needs them: the
+    // dense N x N grid the step of T is written into before it is copied onto the caller's T, and
+    // pgmg_boussinesq_time's five scratch arrays (N * N doubles each); registered allocations
+    double *bq_tout = nullptr;
+    double *bq_scr = nullptr;
 };
 
 namespace pgmg {

@@ -157,6 +157,11 @@ int pgmg_destroy(pgmg_ctx *c)
     }
     for (hipEvent_t e : c->vt_ev)
         if (e) (void)hipEventDestroy(e);
+    for (double *q : {c->bq_tout, c->bq_scr})
+        if (q) {
+            unregister_alloc(q);
+            (void)hipFree(q);
+        }
     if (c->pj_ev0) (void)hipEventDestroy(c->pj_ev0);
     if (c->pj_ev1) (void)hipEventDestroy(c->pj_ev1);
     if (c->ex_ev0) (void)hipEventDestroy(c->ex_ev0);

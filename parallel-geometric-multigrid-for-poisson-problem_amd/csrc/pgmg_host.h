@@ -117,6 +117,26 @@ void launch_vort_wall(const double *psi, long long Pp, double *w, long long Pw, 
                       int mode, const double walls[4], hipStream_t s);
 const char *vort_step_error(double dt, double nu);
 const char *vort_wall_error(int mode, const double walls[4]);
+// what pgmg_boussinesq.hip takes over: k_vort_max on np partials, the events c->vt_ev, and what
+// the context entries refuse after their arguments (`who` names the entry)
+void launch_vort_max(const double *partials, int np, double *vmax, hipStream_t s);
+int vort_events(pgmg_ctx *c);
+int vort_state_check(pgmg_ctx *c, const std::string &who);
+
+// --- pgmg_boussinesq.hip
+// The two passes of the buoyancy-driven flow (include/pgmg.h "Buoyancy-driven flow"), fp64,
+// element (0, 0) and pitch (elements) of every array.  launch_bouss_step: wout and tout = the
+// explicit Euler steps of w and T under psi with the buoyancy source in w's, on grad_grid(N);
+// vmax as in launch_vort_step.  launch_scalar_wall: T's adiabatic walls (mask of PGMG_TWALL_*) in
+// place.  No span checks here (launch_extrap's rule).  bouss_step_error / scalar_wall_error: what
+// the entries refuse in kappa and buoy, in the mask (nullptr: nothing).
+void launch_bouss_step(const double *psi, long long Pp, const double *w, long long Pw, const double *T,
+                       long long Pt, double *wout, long long Pwo, double *tout, long long Pto, int N,
+                       double h, double dt, double nu, double kappa, const double buoy[2],
+                       double *partials, double *vmax, hipStream_t s);
+void launch_scalar_wall(double *T, long long Pt, int N, unsigned adiabatic, hipStream_t s);
+const char *bouss_step_error(double kappa, const double buoy[2]);
+const char *scalar_wall_error(unsigned adiabatic);
 
 // --- pgmg_monitor.hip
 // the damping pass on a level of the FMG pyramid (no norm, nothing waits); fmg_damp_reserve

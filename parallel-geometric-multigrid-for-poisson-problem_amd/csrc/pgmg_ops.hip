@@ -287,6 +287,58 @@ int pgmg_wall_vorticity_grid(const double *d_psi, double *d_w, int N, double h, 
     return PGMG_OK;
 }
 
+// wout and Tout = the explicit Euler steps of w and T under psi with the buoyancy source, on the
+// caller's arrays (pitch N): pgmg_boussinesq_step's pass (pgmg_boussinesq.hip)
+int pgmg_boussinesq_grid(const double *d_psi, const double *d_w, const double *d_T, double *d_wout,
+                         double *d_Tout, int N, double h, double dt, double nu, double kappa,
+                         const double buoy[2], double *vmax, void *stream)
+{
+    const std::string who("pgmg_boussinesq_grid");
+    int e = vort_op_check(who.c_str(), N, h);
+    if (e) return e;
+    if (const char *bad = vort_step_error(dt, nu)) return set_err(PGMG_ERR_ARG, who + ": " + bad);
+    if (const char *bad = bouss_step_error(kappa, buoy)) return set_err(PGMG_ERR_ARG, who + ": " + bad);
+    if (!d_psi || !d_w || !d_T || !d_wout || !d_Tout)
+        return set_err(PGMG_ERR_ARG, who + ": null psi, w, T, wout or Tout");
+    const size_t bytes = (size_t)N * N * sizeof(double);
+    if (!device_range(d_wout, N) || !device_range(d_Tout, N))
+        return set_err(PGMG_ERR_ARG, who + ": an output is not device memory");
+    if (ranges_overlap(d_wout, bytes, d_Tout, bytes)) return set_err(PGMG_ERR_ARG, who + ": the outputs overlap");
+    for (const double *out : {d_wout, d_Tout})
+        for (const double *in : {d_psi, d_w, d_T})
+            if (ranges_overlap(out, bytes, in, bytes))
+                return set_err(PGMG_ERR_ARG, who + ": an output overlaps psi, w or T");
+    hipStream_t s = (hipStream_t)stream;
+    OpScratch *op = nullptr;
+    if ((e = ensure_scratch(s, 0, &op))) return e;
+    const size_t np = (size_t)gradient_blocks(N);
+    if (vmax && (e = ensure_grad(s, *op, np + 1))) return e;
+    double *top = vmax ? op->grad + np : nullptr;
+    launch_bouss_step(d_psi, N, d_w, N, d_T, N, d_wout, N, d_Tout, N, N, h, dt, nu, kappa, buoy,
+                      op->grad, top, s);
+    HIPC(hipGetLastError());
+    if (vmax) {
+        double t = 0.0;
+        HIPC(hipMemcpyAsync(&t, top, sizeof(t), hipMemcpyDeviceToHost, s));
+        HIPC(hipStreamSynchronize(s));
+        *vmax = t;
+    }
+    return PGMG_OK;
+}
+
+// T's adiabatic walls on the caller's array (pitch N): pgmg_boussinesq_step's scalar wall pass
+int pgmg_wall_scalar_grid(double *d_T, int N, unsigned adiabatic, void *stream)
+{
+    const std::string who("pgmg_wall_scalar_grid");
+    if (N < 5 || ((N - 1) & (N - 2)) != 0) return set_err(PGMG_ERR_ARG, who + ": need N = 2^k + 1 with k >= 2");
+    if (const char *bad = scalar_wall_error(adiabatic)) return set_err(PGMG_ERR_ARG, who + ": " + bad);
+    if (!d_T) return set_err(PGMG_ERR_ARG, who + ": null T");
+    if (!device_range(d_T, N)) return set_err(PGMG_ERR_ARG, who + ": T is not device memory");
+    launch_scalar_wall(d_T, N, N, adiabatic, (hipStream_t)stream);
+    HIPC(hipGetLastError());
+    return PGMG_OK;
+}
+
 // fine <- fine + C((fine(2j, 2i) - coarse) * K3) on the caller's arrays (pitches Nf and Nc): the
 // two passes of pgmg_solve_extrap's extrapolation (pgmg_extrap.hip), D dense in the stream's set
 int pgmg_extrap_grid(double *d_fine, const double *d_coarse, int Nf, void *stream)

@@ -23,22 +23,13 @@
 #include <cmath>
 #include <string>
 
-#include "pgmg_grad_dev.h"
 #include "pgmg_host.h"
 #include "pgmg_stop.h"
+#include "pgmg_vort_dev.h"
 
 using namespace pgmg;
 
 namespace pgmg {
-
-using VD2 = V2<double>;
-
-// a lane's share of one row: its pair, and the one value an edge lane loads beside it (lane 0
-// the column left of its pair -- column 0 for the first lane --, lane 63 the column right of it)
-struct VRow {
-    VD2 o;
-    double e;
-};
 
 struct VortArgs {
     const double *p;    // element (0, 0) of psi, pitch Pp
@@ -53,17 +44,6 @@ struct VortArgs {
     int N;
     int band;           // rows per workgroup
 };
-
-// the maximum of one non-negative double over the 64 lanes of a wave (wave_sum's moves; a lane
-// without a source reads 0).  All 64 lanes must be active
-__device__ __forceinline__ double wave_max(double v)
-{
-    v = fmax(v, dpp64<0x111>(v));
-    v = fmax(v, dpp64<0x112>(v));
-    v = fmax(v, dpp64<0x114>(v));
-    v = fmax(v, dpp64<0x118>(v));
-    return fmax(fmax(readlane64(v, 15), readlane64(v, 31)), fmax(readlane64(v, 47), readlane64(v, 63)));
-}
 
 template <bool VMAX>
 __global__ __launch_bounds__(kBlock) void k_vort_step(VortArgs a)
@@ -296,8 +276,13 @@ const char *vort_wall_error(int mode, const double walls[4])
     return nullptr;
 }
 
+void launch_vort_max(const double *partials, int np, double *vmax, hipStream_t s)
+{
+    k_vort_max<<<dim3(1), dim3(kBlock), 0, s>>>(partials, np, vmax);
+}
+
 // the events of pgmg_vorticity_step and pgmg_vorticity_time
-static int vort_events(pgmg_ctx *c)
+int vort_events(pgmg_ctx *c)
 {
     for (hipEvent_t &e : c->vt_ev)
         if (!e) HIPC(hipEventCreate(&e));
@@ -305,7 +290,7 @@ static int vort_events(pgmg_ctx *c)
 }
 
 // what both context entries refuse after their arguments
-static int vort_state_check(pgmg_ctx *c, const std::string &who)
+int vort_state_check(pgmg_ctx *c, const std::string &who)
 {
     if (!c->have_problem) return set_err(PGMG_ERR_STATE, "pgmg_set_problem first");
     if (c->cfg.world > 1)
