@@ -803,7 +803,8 @@ int pgmg_project_time(pgmg_ctx *ctx, int which, int order, int reps, double *ms,
  * Stability is the caller's business: explicit Euler with central differences needs about
  * info->cfl <= 1 and info->diffusion = 4 nu dt / h^2 <= 1 (and a cell Reynolds number
  * |u| h / nu of at most about 2 for a monotone solution).  A non-finite cfl is no error.  The
- * scheme is first order in time and second order in space.  The model is tests/vort_model.py.
+ * scheme is first order in time and second order in space (orders 2 and 3 in time: "Runge-Kutta
+ * vorticity transport" below).  The model is tests/vort_model.py.
  * Errors, all before anything is written.  PGMG_ERR_ARG: a null argument; invalid opts
  * (pgmg_solve's rule); PGMG_MON_ERROR in opts; omega not finite, <= 0 or > 1; dt not finite or
  * <= 0; nu not finite or < 0; a mode other than the two; a wall speed that is not finite; nsteps
@@ -830,6 +831,64 @@ typedef struct pgmg_vort_info {
 int pgmg_vorticity_step(pgmg_ctx *ctx, const pgmg_solve_opts *o, double omega, double dt, double nu,
                         int mode, const double walls[4], int nsteps, pgmg_vort_info *info);
 int pgmg_vorticity_time(pgmg_ctx *ctx, int which, int reps, double *ms_per_pass, double *bytes);
+
+/* ---- Runge-Kutta vorticity transport -----------------------------------------------------------
+ * pgmg_vorticity_step_rk(ctx, opts, omega, dt, nu, mode, walls, order, nsteps, info): the flow of
+ * "Vorticity transport" above advanced by a strong-stability-preserving Runge-Kutta scheme of
+ * order 1, 2 or 3 in time (Shu and Osher's form: every stage is a convex combination of the
+ * vorticity the step started from and one explicit Euler step).  Every convention is that
+ * section's: the state is the context's problem (phi = psi, f = w), fp64, one GPU, synchronous,
+ * expressions evaluated left to right as written, one rounding per operation, no fused
+ * multiply-add.
+ *   E(P, W) is that section's step with the dt and nu of the call: W[y][x] + dt * (nu * lap - adv)
+ *   on the interior and W's frame on the frame -- word for word pgmg_vorticity_grid's output.
+ *   A stage with the coefficients (a, b) and the saved field W0, with e = E(P, W)[y][x]:
+ *     out[y][x] = a * W0[y][x] + b * e          1 <= y, x <= N - 2: a * W0, b * e, their sum
+ *     out's frame = W's frame, word for word    (a -0.0 stays -0.0); W0's frame is never read
+ *   24 B read and 8 B written per point; vmax is "Vorticity transport"'s, of P.
+ *   The stages by order.  Stage 1 is always plain E (the pass of pgmg_vorticity_step itself, not
+ *   the combination with (0, 1)); K3 is the double nearest 1/3 (0x3FD5555555555555) and B3 the
+ *   double nearest 2/3 (0x3FE5555555555555):
+ *     order 1   E
+ *     order 2   E; (0.5, 0.5)                   Heun's method in Shu-Osher form
+ *     order 3   E; (0.75, 0.25); (K3, B3)       Shu and Osher's third-order scheme
+ * Per step, for stage k = 1 .. order:
+ *   1. The wall pass of "Vorticity transport" on f's frame, from the current phi (mode, walls).
+ *   2. k = 1 only: W0 := f, the whole grid as the wall pass left it (a context-owned grid of f's
+ *      shape, allocated on the first call with order > 1, freed by pgmg_destroy).
+ *   3. The stage -- E for k = 1, the combination of f and W0 otherwise --, f and phi read where
+ *      they lie, into pgmg_vorticity_step's scratch grid, which is then copied onto f on the
+ *      stream.  The context's problem is then one with a caller's f, exactly as step 2 of
+ *      pgmg_vorticity_step leaves it.
+ *   4. pgmg_solve_damped(ctx, opts, omega, &info->last), warm-started from the current phi.
+ * After the last step one more wall pass runs.  So a step costs `order` solves; order 1 is bit
+ * for bit pgmg_vorticity_step (phi, f and every field of info but the times); and nsteps = 3 gives
+ * the bits of three calls of one step.  info keeps its layout: steps counts steps; cycles and
+ * sweeps sum over all stage solves; last is the last stage's solve; worst_res and worst_reason
+ * range over all stage solves; cfl comes from the vmax of the last step's last stage; diffusion
+ * is 4 nu dt / h^2; step_ms sums the wall passes, the stages and the copies.
+ * Stability is still the caller's business, but the orders differ in kind.  For w' = lambda w a
+ * step multiplies w by R(z), z = lambda dt: R = 1 + z, 1 + z + z^2/2, 1 + z + z^2/2 + z^3/6.
+ * Central advection has imaginary eigenvalues: of the frozen-velocity operator u d_x + v d_y they
+ * are bounded by (|u| + |v|) / |h|, so |z| <= info->cfl.  On the imaginary axis |R(i s)|^2 is
+ * 1 + s^2 (order 1), 1 + s^4 / 4 (order 2: Heun shares Euler's defect) and 1 - s^4 / 12 +
+ * s^6 / 36 (order 3), which is <= 1 exactly for s <= sqrt(3).  The 5-point diffusion has real
+ * eigenvalues in [-8 nu / h^2, 0], so z >= -2 * info->diffusion, and order 3's |R| <= 1 on the
+ * real axis down to z = -2.51.  So order 3 holds for cfl <= sqrt(3) = 1.73 and diffusion <= 1.25,
+ * each limit taken alone (a step near both at once is outside the region), whatever the
+ * viscosity, nu = 0 included; orders 1 and 2 amplify every advective mode and need the viscosity
+ * to damp it (about cfl <= 1, diffusion <= 1 and a cell Reynolds number of at most about 2, as
+ * above).  The scheme is second order in space.  The model is tests/vort_rk_model.py.
+ * Errors, all before anything is written: everything pgmg_vorticity_step refuses, with its
+ * codes; an order outside 1 .. 3: PGMG_ERR_ARG.
+ * pgmg_vorticity_rk_time: pgmg_vorticity_time's measurement of the stage pass on four
+ * context-owned scratch arrays allocated on the first call (32 N^2 bytes): which = 0 the stage
+ * with its copy back (48 N^2 bytes), which = 1 the stage with vmax, both launches (32 N^2).
+ * Neither phi nor f is written. */
+int pgmg_vorticity_step_rk(pgmg_ctx *ctx, const pgmg_solve_opts *o, double omega, double dt,
+                           double nu, int mode, const double walls[4], int order, int nsteps,
+                           pgmg_vort_info *info);
+int pgmg_vorticity_rk_time(pgmg_ctx *ctx, int which, int reps, double *ms_per_pass, double *bytes);
 
 /* ---- Buoyancy-driven flow ---------------------------------------------------------------------
  * pgmg_boussinesq_step(ctx, opts, omega, p, d_T, nsteps, info): the flow of "Vorticity transport"
@@ -1178,6 +1237,15 @@ int pgmg_vorticity_grid(const double *d_psi, const double *d_w, double *d_out, i
                         double dt, double nu, double *vmax, void *stream);
 int pgmg_wall_vorticity_grid(const double *d_psi, double *d_w, int N, double h, int mode,
                              const double walls[4], void *stream);
+/* The stage pass of pgmg_vorticity_step_rk ("Runge-Kutta vorticity transport" above) on
+ * caller-owned device arrays of doubles at pitch N, under pgmg_vorticity_grid's contract: d_out =
+ * a * d_w0 + b * E(d_psi, d_w) on the interior, d_w's frame on the frame.  d_psi, d_w and d_w0 are
+ * only read; d_w0 may be d_w (or overlap it); d_out must overlap none of the three.  vmax as in
+ * pgmg_vorticity_grid.  pgmg_vorticity_grid's argument errors, an a or b that is not finite, a
+ * null d_w0: PGMG_ERR_ARG, nothing enqueued. */
+int pgmg_vorticity_stage_grid(const double *d_psi, const double *d_w, const double *d_w0,
+                              double *d_out, int N, double h, double dt, double nu, double a,
+                              double b, double *vmax, void *stream);
 /* The two passes of pgmg_boussinesq_step ("Buoyancy-driven flow" above) on caller-owned device
  * arrays of doubles at pitch N, N = 2^k + 1 with k >= 2, under the contract of the two entries
  * above.

@@ -496,16 +496,21 @@ class Solver:
         return ms.value, b.value
 
     def vorticity_step(self, dt, nu, walls=(0.0, 0.0, 0.0, 0.0), free=False, nsteps=1, damp=0.5,
-                       atol=0.0, rtol=0.0, max_cycles=30, check_every=1):
-        """`nsteps` explicit Euler steps of 2D incompressible flow in streamfunction-vorticity form
-        (pgmg_vorticity_step): the context's phi is the streamfunction psi (u = psi_y, v = -psi_x)
+                       atol=0.0, rtol=0.0, max_cycles=30, check_every=1, order=1):
+        """`nsteps` time steps of 2D incompressible flow in streamfunction-vorticity form
+        (order=1: explicit Euler, pgmg_vorticity_step; order=2 or 3: the strong-stability-
+        preserving Runge-Kutta schemes of pgmg_vorticity_step_rk, `order` stages per step, each an
+        Euler pass combined with the vorticity the step started from and followed by its own
+        solve; order 3 is stable for cfl <= 1.73 and diffusion <= 1.25 whatever nu, orders 1 and 2
+        need the viscosity to damp advection; cycles, sweeps and the worst residual then range
+        over all stage solves).  The context's phi is the streamfunction psi (u = psi_y, v = -psi_x)
         and its f the vorticity; start with set_problem(psi0, omega0) (zeros: a cavity at rest).
         Per step: f's frame from psi by Thom's formula with the wall speeds walls = (u on y = 0,
         u on y = a, v on x = 0, v on x = a) -- or +0.0 with free=True (free slip) --, then
         f <- f + dt (nu lap(f) - (psi_y f_x - psi_x f_y)) on the interior, then the damped solve
         of -lap(psi) = f warm-started from the previous psi (state the target as atol, create the
-        Solver with eps < 0).  Stability is the caller's business: keep `.cfl` below about 1 and
-        `.diffusion` = 4 nu dt / h^2 at most 1.  Returns a namespace: steps, cycles and sweeps
+        Solver with eps < 0).  Stability is the caller's business: at orders 1 and 2 keep `.cfl` below
+        about 1 and `.diffusion` = 4 nu dt / h^2 at most 1.  Returns a namespace: steps, cycles and sweeps
         (summed), last (the last step's PgmgSolveInfo), worst_res and worst_reason, cfl, diffusion,
         step_ms, solve_ms, elapsed_ms, history (the last solve's checks).  fp64, one GPU,
         context-owned problems."""
@@ -515,12 +520,28 @@ class Solver:
         o.rtol, o.atol, o.max_cycles, o.check_every = rtol, atol, int(max_cycles), int(check_every)
         w = (C.c_double * 4)(*(float(x) for x in walls))
         info = PgmgVortInfo()
-        check(self.lib.pgmg_vorticity_step(self.h, C.byref(o), float(damp), float(dt), float(nu),
-                                           PGMG_WALL_FREE if free else PGMG_WALL_NOSLIP, w,
-                                           int(nsteps), C.byref(info)), "pgmg_vorticity_step")
+        mode = PGMG_WALL_FREE if free else PGMG_WALL_NOSLIP
+        if int(order) == 1:
+            check(self.lib.pgmg_vorticity_step(self.h, C.byref(o), float(damp), float(dt), float(nu),
+                                               mode, w, int(nsteps), C.byref(info)),
+                  "pgmg_vorticity_step")
+        else:
+            check(self.lib.pgmg_vorticity_step_rk(self.h, C.byref(o), float(damp), float(dt),
+                                                  float(nu), mode, w, int(order), int(nsteps),
+                                                  C.byref(info)), "pgmg_vorticity_step_rk")
         out = SimpleNamespace(**{name: getattr(info, name) for name, _ in PgmgVortInfo._fields_})
         out.history = self.history()
         return out
+
+    def vorticity_rk_time(self, which, reps=20):
+        """(mean device ms, algorithmic bytes) of one Runge-Kutta stage pass of vorticity_step
+        (order 2 or 3) over `reps` back to back on context-owned arrays (pgmg_vorticity_rk_time;
+        measurement): which=0 the stage with its copy back, which=1 the stage with the velocity
+        maximum.  Leaves phi and f alone."""
+        ms, b = C.c_double(), C.c_double()
+        check(self.lib.pgmg_vorticity_rk_time(self.h, int(which), int(reps), C.byref(ms), C.byref(b)),
+              "pgmg_vorticity_rk_time")
+        return ms.value, b.value
 
     def vorticity_time(self, which, reps=20):
         """(mean device ms, algorithmic bytes) of one pass of vorticity_step over `reps` back to
@@ -1095,6 +1116,21 @@ class _Ops:
         check(load().pgmg_vorticity_grid(self._ptr(psi), self._ptr(w), self._ptr(out), N, float(h),
                                          float(dt), float(nu), C.byref(m) if vmax else None, stream),
               "pgmg_vorticity_grid")
+        return (out, m.value) if vmax else out
+
+    def vorticity_stage(self, psi, w, w0, out, h, dt, nu, a, b, vmax=False, stream=None):
+        """out = a * w0 + b * e on the interior, e = ops.vorticity_step's value of w under psi, and
+        w's frame on the frame: a Runge-Kutta stage in Shu-Osher form (pgmg_vorticity_stage_grid).
+        N x N float64 device arrays, N = 2^k + 1, k >= 2; a and b finite; w0 may be w; out must
+        overlap none of psi, w and w0.  vmax as in ops.vorticity_step."""
+        N = psi.shape[0]
+        for t in (psi, w, w0, out):
+            assert tuple(t.shape) == (N, N), t.shape
+        m = C.c_double()
+        check(load().pgmg_vorticity_stage_grid(self._ptr(psi), self._ptr(w), self._ptr(w0),
+                                               self._ptr(out), N, float(h), float(dt), float(nu),
+                                               float(a), float(b), C.byref(m) if vmax else None,
+                                               stream), "pgmg_vorticity_stage_grid")
         return (out, m.value) if vmax else out
 
     def wall_vorticity(self, psi, w, h, walls=(0.0, 0.0, 0.0, 0.0), free=False, stream=None):

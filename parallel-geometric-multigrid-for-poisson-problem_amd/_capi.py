@@ -213,6 +213,10 @@ SIGNATURES = [
     ("pgmg_vorticity_step", C.c_int, [_P, C.POINTER(PgmgSolveOpts), C.c_double, C.c_double,
                                       C.c_double, C.c_int, _DP, C.c_int, C.POINTER(PgmgVortInfo)]),
     ("pgmg_vorticity_time", C.c_int, [_P, C.c_int, C.c_int, _DP, _DP]),
+    ("pgmg_vorticity_step_rk", C.c_int, [_P, C.POINTER(PgmgSolveOpts), C.c_double, C.c_double,
+                                         C.c_double, C.c_int, _DP, C.c_int, C.c_int,
+                                         C.POINTER(PgmgVortInfo)]),
+    ("pgmg_vorticity_rk_time", C.c_int, [_P, C.c_int, C.c_int, _DP, _DP]),
     ("pgmg_boussinesq_step", C.c_int, [_P, C.POINTER(PgmgSolveOpts), C.c_double,
                                        C.POINTER(PgmgBoussParams), _P, C.c_int,
                                        C.POINTER(PgmgBoussInfo)]),
@@ -267,6 +271,8 @@ SIGNATURES = [
     ("pgmg_vorticity_grid", C.c_int, [_P, _P, _P, C.c_int, C.c_double, C.c_double, C.c_double, _DP,
                                       _P]),
     ("pgmg_wall_vorticity_grid", C.c_int, [_P, _P, C.c_int, C.c_double, C.c_int, _DP, _P]),
+    ("pgmg_vorticity_stage_grid", C.c_int, [_P, _P, _P, _P, C.c_int, C.c_double, C.c_double,
+                                            C.c_double, C.c_double, C.c_double, _DP, _P]),
     ("pgmg_boussinesq_grid", C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_double, C.c_double,
                                        C.c_double, C.c_double, _DP, _DP, _P]),
     ("pgmg_wall_scalar_grid", C.c_int, [_P, C.c_int, C.c_uint, _P]),

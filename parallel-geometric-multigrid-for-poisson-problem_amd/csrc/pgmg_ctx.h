@@ -286,6 +286,11 @@ struct pgmg_ctx {
     pgmg::Grid vt_out;
     hipEvent_t vt_ev[2] = {};
     double *vt_scr = nullptr;
+    // pgmg_vorticity_step_rk (pgmg_vort_rk.hip): the grid of f's shape that keeps the omega a step
+    // started from, made on the first call with order > 1, and pgmg_vorticity_rk_time's four
+    // scratch arrays (N * N doubles each, a registered allocation)
+    pgmg::Grid vt_w0;
+    double *vt_rk_scr = nullptr;
     // pgmg_boussinesq_step (pgmg_boussinesq.hip), made on the first call that needs them: the
     // dense N x N grid the step of T is written into before it is copied onto the caller's T, and
     // pgmg_boussinesq_time's five scratch arrays (N * N doubles each); registered allocations

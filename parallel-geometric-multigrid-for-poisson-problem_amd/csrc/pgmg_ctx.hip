@@ -157,7 +157,8 @@ int pgmg_destroy(pgmg_ctx *c)
     }
     for (hipEvent_t e : c->vt_ev)
         if (e) (void)hipEventDestroy(e);
-    for (double *q : {c->bq_tout, c->bq_scr})
+    free_grid(c->vt_w0);
+    for (double *q : {c->vt_rk_scr, c->bq_tout, c->bq_scr})
         if (q) {
             unregister_alloc(q);
             (void)hipFree(q);

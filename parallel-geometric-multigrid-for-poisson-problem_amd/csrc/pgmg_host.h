@@ -122,6 +122,20 @@ const char *vort_wall_error(int mode, const double walls[4]);
 void launch_vort_max(const double *partials, int np, double *vmax, hipStream_t s);
 int vort_events(pgmg_ctx *c);
 int vort_state_check(pgmg_ctx *c, const std::string &who);
+// the time loop of pgmg_vorticity_step (order 1) and pgmg_vorticity_step_rk: every refusal of the
+// two entries under the name `who`, then nsteps steps of `order` stages
+int vort_advance(pgmg_ctx *c, const pgmg_solve_opts *o, double omega, double dt, double nu, int mode,
+                 const double walls[4], int order, int nsteps, pgmg_vort_info *info,
+                 const std::string &who);
+
+// --- pgmg_vort_rk.hip
+// A Runge-Kutta stage in Shu-Osher form (include/pgmg.h "Runge-Kutta vorticity transport"), under
+// launch_vort_step's conventions: out = a * w0 + b * (the Euler step of w under psi) on the
+// interior, w's frame on the frame; w0 may be w; vmax as in launch_vort_step
+void launch_vort_stage(const double *psi, long long Pp, const double *w, long long Pw,
+                       const double *w0, long long P0, double *out, long long Po, int N, double h,
+                       double dt, double nu, double a, double b, double *partials, double *vmax,
+                       hipStream_t s);
 
 // --- pgmg_boussinesq.hip
 // The two passes of the buoyancy-driven flow (include/pgmg.h "Buoyancy-driven flow"), fp64,

@@ -269,6 +269,40 @@ int pgmg_vorticity_grid(const double *d_psi, const double *d_w, double *d_out, i
     return PGMG_OK;
 }
 
+// out = a * w0 + b * (the explicit Euler step of omega under psi) on the caller's arrays (pitch
+// N): pgmg_vorticity_step_rk's stage pass (pgmg_vort_rk.hip); w0 may be w
+int pgmg_vorticity_stage_grid(const double *d_psi, const double *d_w, const double *d_w0,
+                              double *d_out, int N, double h, double dt, double nu, double a,
+                              double b, double *vmax, void *stream)
+{
+    const std::string who("pgmg_vorticity_stage_grid");
+    int e = vort_op_check(who.c_str(), N, h);
+    if (e) return e;
+    if (const char *bad = vort_step_error(dt, nu)) return set_err(PGMG_ERR_ARG, who + ": " + bad);
+    if (!std::isfinite(a) || !std::isfinite(b)) return set_err(PGMG_ERR_ARG, who + ": a and b must be finite");
+    if (!d_psi || !d_w || !d_w0 || !d_out) return set_err(PGMG_ERR_ARG, who + ": null psi, w, w0 or out");
+    const size_t bytes = (size_t)N * N * sizeof(double);
+    if (!device_range(d_out, N)) return set_err(PGMG_ERR_ARG, who + ": out is not device memory");
+    for (const double *in : {d_psi, d_w, d_w0})
+        if (ranges_overlap(d_out, bytes, in, bytes))
+            return set_err(PGMG_ERR_ARG, who + ": out overlaps psi, w or w0");
+    hipStream_t s = (hipStream_t)stream;
+    OpScratch *op = nullptr;
+    if ((e = ensure_scratch(s, 0, &op))) return e;
+    const size_t np = (size_t)gradient_blocks(N);
+    if (vmax && (e = ensure_grad(s, *op, np + 1))) return e;
+    double *top = vmax ? op->grad + np : nullptr;
+    launch_vort_stage(d_psi, N, d_w, N, d_w0, N, d_out, N, N, h, dt, nu, a, b, op->grad, top, s);
+    HIPC(hipGetLastError());
+    if (vmax) {
+        double t = 0.0;
+        HIPC(hipMemcpyAsync(&t, top, sizeof(t), hipMemcpyDeviceToHost, s));
+        HIPC(hipStreamSynchronize(s));
+        *vmax = t;
+    }
+    return PGMG_OK;
+}
+
 // the frame of omega from psi on the caller's arrays (pitch N): pgmg_vorticity_step's wall pass
 int pgmg_wall_vorticity_grid(const double *d_psi, double *d_w, int N, double h, int mode,
                              const double walls[4], void *stream)

@@ -1,7 +1,8 @@
 // pgmg_vorticity.hip — streamfunction-vorticity flow (include/pgmg.h "Vorticity transport";
 // DESIGN.md §4h): k_vort_step, k_vort_max, k_vort_wall, pgmg_vorticity_step and
 // pgmg_vorticity_time (pgmg_vorticity_grid and pgmg_wall_vorticity_grid, on the caller's arrays:
-// pgmg_ops.hip).
+// pgmg_ops.hip), and vort_advance, the time loop pgmg_vorticity_step shares with
+// pgmg_vorticity_step_rk (pgmg_vort_rk.hip: the Runge-Kutta stage pass k_vort_stage).
 //
 // The problem the library solves, -lap(phi) = f with phi's frame as Dirichlet data, is the
 // streamfunction equation: phi = psi, f = omega, u = psi_y, v = -psi_x.  One explicit Euler step
@@ -299,23 +300,23 @@ int vort_state_check(pgmg_ctx *c, const std::string &who)
     return PGMG_OK;
 }
 
-}  // namespace pgmg
-
-extern "C" {
-
-int pgmg_vorticity_step(pgmg_ctx *c, const pgmg_solve_opts *o, double omega, double dt, double nu,
-                        int mode, const double walls[4], int nsteps, pgmg_vort_info *info)
+// pgmg_vorticity_step (order 1) and pgmg_vorticity_step_rk (pgmg_vort_rk.hip): what they refuse,
+// then nsteps steps of `order` stages each (include/pgmg.h "Runge-Kutta vorticity transport").
+// Stage 1 is the Euler pass; order 1 runs nothing else
+int vort_advance(pgmg_ctx *c, const pgmg_solve_opts *o, double omega, double dt, double nu, int mode,
+                 const double walls[4], int order, int nsteps, pgmg_vort_info *info,
+                 const std::string &who)
 {
-    const std::string who("pgmg_vorticity_step");
     if (!c || !o || !walls || !info) return set_err(PGMG_ERR_ARG, "null argument");
     if (const char *bad = solve_opts_error(*o)) return set_err(PGMG_ERR_ARG, who + ": " + bad);
     if (o->monitor & PGMG_MON_ERROR)
         return set_err(PGMG_ERR_ARG, who + ": PGMG_MON_ERROR needs the analytic problem; the "
                                            "right-hand side is the vorticity");
-    PGMG_TRY(damp_omega_check(omega, "pgmg_vorticity_step"));
+    PGMG_TRY(damp_omega_check(omega, who.c_str()));
     if (const char *bad = vort_step_error(dt, nu)) return set_err(PGMG_ERR_ARG, who + ": " + bad);
     if (const char *bad = vort_wall_error(mode, walls)) return set_err(PGMG_ERR_ARG, who + ": " + bad);
     if (nsteps < 1) return set_err(PGMG_ERR_ARG, who + ": nsteps must be at least 1");
+    if (order < 1 || order > 3) return set_err(PGMG_ERR_ARG, who + ": order must be 1, 2 or 3");
     PGMG_TRY(vort_state_check(c, who));
     if (c->ext_phi)
         return set_err(PGMG_ERR_STATE, who + ": the problem is bound to the caller's arrays "
@@ -331,45 +332,63 @@ int pgmg_vorticity_step(pgmg_ctx *c, const pgmg_solve_opts *o, double omega, dou
     // the scratch grid the step is written into: f's shape (the f grid's address is part of the
     // cycles' captured graphs, so the result is copied onto it instead of swapping the records)
     if (!c->vt_out.base) PGMG_TRY(alloc_grid(c->vt_out, L));
+    // the grid a Runge-Kutta step keeps the omega it started from in (order > 1 only)
+    if (order > 1 && !c->vt_w0.base) PGMG_TRY(alloc_grid(c->vt_w0, L));
     PGMG_TRY(grad_reserve(c, gradient_blocks(N)));
     double *const total = c->grad_buf + c->grad_cap;
     double *const F = G<double>(L.F), *const out = G<double>(c->vt_out);
+    double *const W0 = order > 1 ? G<double>(c->vt_w0) : nullptr;
     PGMG_TRY(check_span(F, L.P, 8, 0, N - 1, 0, N - 1, "k_vort_step omega"));
     PGMG_TRY(check_span(out, L.P, 8, 0, N - 1, 0, N - 1, "k_vort_step out"));
+    if (W0) PGMG_TRY(check_span(W0, L.P, 8, 0, N - 1, 0, N - 1, "k_vort_stage omega0"));
     // (rows 0 .. N of a level-0 grid are one contiguous range: see pgmg_set_problem)
     const size_t bytes = (size_t)L.P * L.es * (size_t)N;
+    // the Shu-Osher coefficients (a, b) of stages 2 and 3, by order (stage 1 is the Euler pass)
+    const double K3 = 0x1.5555555555555p-2, B3 = 0x1.5555555555555p-1;
+    const double coef[4][2][2] = {{}, {}, {{0.5, 0.5}, {}}, {{0.75, 0.25}, {K3, B3}}};
     info->worst_res = -1.0;
     double vmax = 0.0;
     for (int n = 0; n < nsteps; ++n) {
-        // 1. omega's frame from the current psi; 2. the step, psi where it lies now (the
-        // cross-fused cycles rotate the grids), and its copy back onto f
-        const double *const psi = G<double>(L.A);
-        PGMG_TRY(check_span(psi, L.P, 8, 0, N - 1, 0, N - 1, "k_vort_step psi"));
-        HIPC(hipEventRecord(c->vt_ev[0], c->s));
-        launch_vort_wall(psi, L.P, F, L.P, N, h, mode, walls, c->s);
-        launch_vort_step(psi, L.P, F, L.P, out, L.P, N, h, dt, nu, c->grad_buf, total, c->s);
-        HIPC(hipGetLastError());
-        HIPC(hipMemcpyAsync(row_ptr(L.F, 0, L.P, L.es), row_ptr(c->vt_out, 0, L.P, L.es), bytes,
-                            hipMemcpyDeviceToDevice, c->s));
-        HIPC(hipEventRecord(c->vt_ev[1], c->s));
-        HIPC(hipMemcpyAsync(&vmax, total, sizeof(double), hipMemcpyDeviceToHost, c->s));
-        PGMG_TRY(set_problem_rhs_on_device(c));   // (waits for the stream)
-        float ms = 0.f;
-        HIPC(hipEventElapsedTime(&ms, c->vt_ev[0], c->vt_ev[1]));
-        info->step_ms += ms;
-        // 3. the solve, warm-started from the previous psi
-        PGMG_TRY(pgmg_solve_damped(c, o, omega, &info->last));
-        long long sweeps = 0;
-        PGMG_TRY(pgmg_stats(c, &sweeps, nullptr));
-        info->steps = n + 1;
-        info->cycles += info->last.cycles;
-        info->sweeps += sweeps;
-        info->solve_ms += info->last.elapsed_ms;
-        // (a NaN residual compares false: it takes the place of any finite one, and keeps it)
-        if (!(info->last.res <= info->worst_res) && !std::isnan(info->worst_res)) {
-            info->worst_res = info->last.res;
-            info->worst_reason = info->last.reason;
+        for (int k = 0; k < order; ++k) {
+            // 1. omega's frame from the current psi; 2. the stage, psi where it lies now (the
+            // cross-fused cycles rotate the grids), and its copy back onto f
+            const double *const psi = G<double>(L.A);
+            PGMG_TRY(check_span(psi, L.P, 8, 0, N - 1, 0, N - 1, "k_vort_step psi"));
+            HIPC(hipEventRecord(c->vt_ev[0], c->s));
+            launch_vort_wall(psi, L.P, F, L.P, N, h, mode, walls, c->s);
+            if (k == 0) {
+                if (W0)
+                    HIPC(hipMemcpyAsync(row_ptr(c->vt_w0, 0, L.P, L.es), row_ptr(L.F, 0, L.P, L.es),
+                                        bytes, hipMemcpyDeviceToDevice, c->s));
+                launch_vort_step(psi, L.P, F, L.P, out, L.P, N, h, dt, nu, c->grad_buf, total, c->s);
+            } else {
+                launch_vort_stage(psi, L.P, F, L.P, W0, L.P, out, L.P, N, h, dt, nu,
+                                  coef[order][k - 1][0], coef[order][k - 1][1], c->grad_buf, total,
+                                  c->s);
+            }
+            HIPC(hipGetLastError());
+            HIPC(hipMemcpyAsync(row_ptr(L.F, 0, L.P, L.es), row_ptr(c->vt_out, 0, L.P, L.es), bytes,
+                                hipMemcpyDeviceToDevice, c->s));
+            HIPC(hipEventRecord(c->vt_ev[1], c->s));
+            HIPC(hipMemcpyAsync(&vmax, total, sizeof(double), hipMemcpyDeviceToHost, c->s));
+            PGMG_TRY(set_problem_rhs_on_device(c));   // (waits for the stream)
+            float ms = 0.f;
+            HIPC(hipEventElapsedTime(&ms, c->vt_ev[0], c->vt_ev[1]));
+            info->step_ms += ms;
+            // 3. the solve, warm-started from the previous psi
+            PGMG_TRY(pgmg_solve_damped(c, o, omega, &info->last));
+            long long sweeps = 0;
+            PGMG_TRY(pgmg_stats(c, &sweeps, nullptr));
+            info->cycles += info->last.cycles;
+            info->sweeps += sweeps;
+            info->solve_ms += info->last.elapsed_ms;
+            // (a NaN residual compares false: it takes the place of any finite one, and keeps it)
+            if (!(info->last.res <= info->worst_res) && !std::isnan(info->worst_res)) {
+                info->worst_res = info->last.res;
+                info->worst_reason = info->last.reason;
+            }
         }
+        info->steps = n + 1;
     }
     // the returned omega's frame belongs to the returned psi
     HIPC(hipEventRecord(c->vt_ev[0], c->s));
@@ -385,6 +404,16 @@ int pgmg_vorticity_step(pgmg_ctx *c, const pgmg_solve_opts *o, double omega, dou
     info->elapsed_ms =
         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return PGMG_OK;
+}
+
+}  // namespace pgmg
+
+extern "C" {
+
+int pgmg_vorticity_step(pgmg_ctx *c, const pgmg_solve_opts *o, double omega, double dt, double nu,
+                        int mode, const double walls[4], int nsteps, pgmg_vort_info *info)
+{
+    return vort_advance(c, o, omega, dt, nu, mode, walls, 1, nsteps, info, "pgmg_vorticity_step");
 }
 
 int pgmg_vorticity_time(pgmg_ctx *c, int which, int reps, double *ms_per_pass, double *bytes)
