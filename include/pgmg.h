@@ -939,7 +939,8 @@ int pgmg_vorticity_rk_time(pgmg_ctx *ctx, int which, int reps, double *ms_per_pa
  * one step.  info->flow is filled as pgmg_vorticity_step fills its info (cfl from the last step's
  * vmax, diffusion = 4 nu dt / h^2); diffusion_t = 4 kappa dt / h^2.  Stability is the caller's
  * business: cfl, diffusion and diffusion_t at most about 1.  The scheme is first order in time
- * and second order in space.  The model is tests/bouss_model.py.
+ * and second order in space (orders 2 and 3 in time: "Runge-Kutta buoyancy-driven flow" below).
+ * The model is tests/bouss_model.py.
  * Errors, all before anything is written.  PGMG_ERR_ARG: everything pgmg_vorticity_step refuses
  * (dt, nu, mode and walls read from p); a null p or d_T; a d_T that is not device memory; kappa
  * not finite or < 0; a buoy component that is not finite; an adiabatic bit above 8.
@@ -966,6 +967,64 @@ typedef struct pgmg_bouss_info {
 int pgmg_boussinesq_step(pgmg_ctx *ctx, const pgmg_solve_opts *o, double omega,
                          const pgmg_bouss_params *p, double *d_T, int nsteps, pgmg_bouss_info *info);
 int pgmg_boussinesq_time(pgmg_ctx *ctx, int which, int reps, double *ms_per_pass, double *bytes);
+
+/* ---- Runge-Kutta buoyancy-driven flow -----------------------------------------------------------
+ * pgmg_boussinesq_step_rk(ctx, opts, omega, p, d_T, order, nsteps, info): the flow of
+ * "Buoyancy-driven flow" above advanced by the strong-stability-preserving Runge-Kutta schemes of
+ * "Runge-Kutta vorticity transport", order 1, 2 or 3 in time.  Every convention is that of those
+ * two sections: the state is the context's problem (phi = psi, f = w) and the caller's d_T, fp64,
+ * one GPU, synchronous, expressions evaluated left to right as written, one rounding per
+ * operation, no fused multiply-add.
+ *   EW(P, W, T) and ET(P, W, T) are "Buoyancy-driven flow"'s Wout and Tout with the dt, nu, kappa
+ *   and buoy of the call -- word for word pgmg_boussinesq_grid's outputs.
+ *   A stage with the coefficients (a, b) and the saved fields W0 and T0, with ew = EW[y][x] and
+ *   et = ET[y][x]:
+ *     wout[y][x] = a * W0[y][x] + b * ew        1 <= y, x <= N - 2: a * W0, b * ew, their sum
+ *     tout[y][x] = a * T0[y][x] + b * et        the same; one (a, b) serves both fields
+ *     wout's frame = W's frame, tout's frame = T's frame, word for word (a -0.0 stays -0.0); the
+ *     frames of W0 and T0 are never read
+ *   40 B read and 16 B written per point; vmax is "Vorticity transport"'s, of P.
+ *   The stages by order are "Runge-Kutta vorticity transport"'s: stage 1 is always the plain Euler
+ *   pass (pgmg_boussinesq_step's own, not the combination with (0, 1)); order 2 adds (0.5, 0.5);
+ *   order 3 adds (0.75, 0.25) and (K3, B3), K3 = 0x3FD5555555555555, B3 = 0x3FE5555555555555.
+ * Per step, for stage k = 1 .. order:
+ *   1. Both wall passes: "Vorticity transport"'s on f's frame from the current phi, and the
+ *      scalar wall pass on d_T's frame.
+ *   2. k = 1 only: W0 := f and T0 := d_T, the whole grids as the wall passes left them (W0 is
+ *      pgmg_vorticity_step_rk's grid; T0 is a context-owned dense N x N grid, allocated on the
+ *      first call with order > 1, freed by pgmg_destroy).
+ *   3. The stage -- the Euler pass for k = 1, the combination otherwise --, phi, f and d_T read
+ *      where they lie, into pgmg_boussinesq_step's two scratch grids, which are then copied on the
+ *      stream onto f and onto d_T: d_T holds stage values during the call and the new temperature
+ *      after it.  The context's problem is then one with a caller's f.
+ *   4. pgmg_solve_damped(ctx, opts, omega, &info->flow.last), warm-started from the current phi.
+ * After the last step both wall passes run once more.  So a step costs `order` solves; order 1 is
+ * bit for bit pgmg_boussinesq_step (phi, f, T and every field of info but the times); and nsteps
+ * = 3 gives the bits of three calls of one step.  info->flow is filled as pgmg_vorticity_step_rk
+ * fills its info (steps counts steps; the sums and worst_* range over all stage solves; cfl comes
+ * from the vmax of the last step's last stage); diffusion_t = 4 kappa dt / h^2.
+ * Stability.  Beside the advective and diffusive eigenvalues of "Runge-Kutta vorticity transport"
+ * the coupling w_t = by T_x, T_t = -v T_y is an oscillator (internal gravity waves): in a stable
+ * stratification T_y = G a mode of wavenumbers (kx, ky) has the frequency n = sqrt(by G) kx /
+ * |k| <= sqrt(by G), purely imaginary eigenvalues whatever nu and kappa are.  With s = n dt, a
+ * step multiplies the mode by |R(i s)|^2 = 1 + s^2 at order 1 -- unstable for every s > 0 that the
+ * diffusion does not reach --, by 1 + s^4 / 4 at order 2, a slow growth that a little diffusion
+ * pays for, and by 1 - s^4 / 12 + s^6 / 36 <= 1 at order 3 for s <= sqrt(3).  So order 3 covers
+ * buoyancy oscillations and advection up to cfl-like numbers of sqrt(3) = 1.73 and diffusion
+ * numbers of 1.25 (each limit taken alone); order 1 needs cfl, diffusion and diffusion_t of at
+ * most about 1 and enough diffusion to damp both.  The scheme is second order in space.  The
+ * model is tests/bouss_rk_model.py.
+ * Errors, all before anything is written: everything pgmg_boussinesq_step refuses, with its
+ * codes; an order outside 1 .. 3: PGMG_ERR_ARG.
+ * pgmg_boussinesq_rk_time: pgmg_boussinesq_time's measurement of the stage pass on seven
+ * context-owned scratch arrays allocated on the first call (56 N^2 bytes): which = 0 the stage
+ * with both copies back (88 N^2 bytes), which = 1 the stage with vmax, both launches (56 N^2);
+ * which = 2 and 3 are 0 and 1 with the pass's other built depth of loads in flight (DESIGN.md §4j;
+ * the entries never launch it).  Neither phi, f nor any caller array is written. */
+int pgmg_boussinesq_step_rk(pgmg_ctx *ctx, const pgmg_solve_opts *o, double omega,
+                            const pgmg_bouss_params *p, double *d_T, int order, int nsteps,
+                            pgmg_bouss_info *info);
+int pgmg_boussinesq_rk_time(pgmg_ctx *ctx, int which, int reps, double *ms_per_pass, double *bytes);
 
 /* ---- Mixed-precision refinement ----------------------------------------------------------
  * pgmg_solve_mixed(ctx, opts, nu, omega, info): fp64 solutions from fp32 multigrid corrections
@@ -1260,6 +1319,17 @@ int pgmg_boussinesq_grid(const double *d_psi, const double *d_w, const double *d
                          double *d_Tout, int N, double h, double dt, double nu, double kappa,
                          const double buoy[2], double *vmax, void *stream);
 int pgmg_wall_scalar_grid(double *d_T, int N, unsigned adiabatic, void *stream);
+/* The stage pass of pgmg_boussinesq_step_rk ("Runge-Kutta buoyancy-driven flow" above) on
+ * caller-owned device arrays of doubles at pitch N, under pgmg_boussinesq_grid's contract: d_wout
+ * = a * d_w0 + b * EW and d_Tout = a * d_T0 + b * ET on the interior, d_w's and d_T's frames on the
+ * frames.  The five inputs are only read; d_w0 may be d_w and d_T0 may be d_T (or overlap them);
+ * an output must not overlap an input or the other output.  vmax == NULL: asynchronous on
+ * `stream`; otherwise synchronous.  pgmg_boussinesq_grid's argument errors, an a or b that is not
+ * finite, a null d_w0 or d_T0: PGMG_ERR_ARG, nothing enqueued. */
+int pgmg_boussinesq_stage_grid(const double *d_psi, const double *d_w, const double *d_T,
+                               const double *d_w0, const double *d_T0, double *d_wout, double *d_Tout,
+                               int N, double h, double dt, double nu, double kappa,
+                               const double buoy[2], double a, double b, double *vmax, void *stream);
 /* The two passes of pgmg_solve_mixed ("Mixed-precision refinement" above) on caller-owned device
  * arrays at pitch N, N = 2^k + 1 with k >= 2: x and f fp64, g and e fp32.
  * pgmg_defect_grid: g = (float)(r * scale) on the interior, +0.0f on the frame, r the fp64 residual

@@ -554,8 +554,12 @@ class Solver:
 
     def boussinesq_step(self, T, dt, nu, kappa, buoy=(0.0, 1.0), walls=(0.0, 0.0, 0.0, 0.0),
                         free=False, adiabatic=("bottom", "top"), nsteps=1, damp=0.5, atol=0.0,
-                        rtol=0.0, max_cycles=30, check_every=1):
-        """`nsteps` explicit Euler steps of buoyancy-driven flow (pgmg_boussinesq_step):
+                        rtol=0.0, max_cycles=30, check_every=1, order=1):
+        """`nsteps` time steps of buoyancy-driven flow (order=1: explicit Euler,
+        pgmg_boussinesq_step; order=2 or 3: the strong-stability-preserving Runge-Kutta schemes of
+        pgmg_boussinesq_step_rk, `order` stages per step with one (a, b) for f and T, each stage
+        followed by its own solve; the buoyancy coupling oscillates on the imaginary axis, which
+        order 3 covers up to sqrt(3), order 2 nearly and Euler not at all):
         vorticity_step's flow carrying the temperature T, which feeds back into the vorticity:
         f_t + u f_x + v f_y = nu lap(f) + (by T_x - bx T_y), T_t + u T_x + v T_y = kappa lap(T),
         buoy = (bx, by) (gravity along -y: (0, g beta)).  T: a contiguous N x N float64 CUDA
@@ -581,8 +585,13 @@ class Solver:
         p.walls = (C.c_double * 4)(*(float(x) for x in walls))
         p.adiabatic = twall_mask(adiabatic)
         info = PgmgBoussInfo()
-        check(self.lib.pgmg_boussinesq_step(self.h, C.byref(o), float(damp), C.byref(p), _dptr(T),
-                                            int(nsteps), C.byref(info)), "pgmg_boussinesq_step")
+        if int(order) == 1:
+            check(self.lib.pgmg_boussinesq_step(self.h, C.byref(o), float(damp), C.byref(p), _dptr(T),
+                                                int(nsteps), C.byref(info)), "pgmg_boussinesq_step")
+        else:
+            check(self.lib.pgmg_boussinesq_step_rk(self.h, C.byref(o), float(damp), C.byref(p),
+                                                   _dptr(T), int(order), int(nsteps), C.byref(info)),
+                  "pgmg_boussinesq_step_rk")
         out = SimpleNamespace(**{name: getattr(info.flow, name) for name, _ in PgmgVortInfo._fields_})
         out.diffusion_t = info.diffusion_t
         out.history = self.history()
@@ -596,6 +605,17 @@ class Solver:
         ms, b = C.c_double(), C.c_double()
         check(self.lib.pgmg_boussinesq_time(self.h, int(which), int(reps), C.byref(ms), C.byref(b)),
               "pgmg_boussinesq_time")
+        return ms.value, b.value
+
+    def boussinesq_rk_time(self, which, reps=20):
+        """(mean device ms, algorithmic bytes) of one Runge-Kutta stage pass of boussinesq_step
+        (order 2 or 3) over `reps` back to back on context-owned arrays (pgmg_boussinesq_rk_time;
+        measurement): which=0 the stage with both copies back, which=1 the stage with the velocity
+        maximum; 2 and 3 the same at the pass's other built depth.  Leaves phi, f and every
+        caller's array alone."""
+        ms, b = C.c_double(), C.c_double()
+        check(self.lib.pgmg_boussinesq_rk_time(self.h, int(which), int(reps), C.byref(ms), C.byref(b)),
+              "pgmg_boussinesq_rk_time")
         return ms.value, b.value
 
     def velocity(self, u=None, v=None):
@@ -1161,6 +1181,26 @@ class _Ops:
                                           self._ptr(w_out), self._ptr(T_out), N, float(h), float(dt),
                                           float(nu), float(kappa), b, C.byref(m) if vmax else None,
                                           stream), "pgmg_boussinesq_grid")
+        return (w_out, T_out, m.value) if vmax else (w_out, T_out)
+
+    def boussinesq_stage(self, psi, w, T, w0, T0, w_out, T_out, h, dt, nu, kappa, buoy, a, b,
+                         vmax=False, stream=None):
+        """w_out = a * w0 + b * ew and T_out = a * T0 + b * et on the interior, ew and et
+        ops.boussinesq_step's values of w and T under psi, and the frames of w and T on the frames:
+        a Runge-Kutta stage in Shu-Osher form (pgmg_boussinesq_stage_grid).  N x N float64 device
+        arrays, N = 2^k + 1, k >= 2; a and b finite; w0 may be w and T0 may be T; an output must
+        not overlap an input or the other output.  vmax as in ops.boussinesq_step."""
+        N = psi.shape[0]
+        for t in (psi, w, T, w0, T0, w_out, T_out):
+            assert tuple(t.shape) == (N, N), t.shape
+        m = C.c_double()
+        bb = (C.c_double * 2)(*(float(x) for x in buoy))
+        check(load().pgmg_boussinesq_stage_grid(self._ptr(psi), self._ptr(w), self._ptr(T),
+                                                self._ptr(w0), self._ptr(T0), self._ptr(w_out),
+                                                self._ptr(T_out), N, float(h), float(dt), float(nu),
+                                                float(kappa), bb, float(a), float(b),
+                                                C.byref(m) if vmax else None, stream),
+              "pgmg_boussinesq_stage_grid")
         return (w_out, T_out, m.value) if vmax else (w_out, T_out)
 
     def wall_scalar(self, T, adiabatic, stream=None):

@@ -221,6 +221,10 @@ SIGNATURES = [
                                        C.POINTER(PgmgBoussParams), _P, C.c_int,
                                        C.POINTER(PgmgBoussInfo)]),
     ("pgmg_boussinesq_time", C.c_int, [_P, C.c_int, C.c_int, _DP, _DP]),
+    ("pgmg_boussinesq_step_rk", C.c_int, [_P, C.POINTER(PgmgSolveOpts), C.c_double,
+                                          C.POINTER(PgmgBoussParams), _P, C.c_int, C.c_int,
+                                          C.POINTER(PgmgBoussInfo)]),
+    ("pgmg_boussinesq_rk_time", C.c_int, [_P, C.c_int, C.c_int, _DP, _DP]),
     ("pgmg_solve_mixed", C.c_int, [_P, C.POINTER(PgmgSolveOpts), C.c_int, C.c_double,
                                    C.POINTER(PgmgMixedInfo)]),
     ("pgmg_mixed_time", C.c_int, [_P, C.c_int, C.c_int, _DP, _DP]),
@@ -276,6 +280,9 @@ SIGNATURES = [
     ("pgmg_boussinesq_grid", C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_double, C.c_double,
                                        C.c_double, C.c_double, _DP, _DP, _P]),
     ("pgmg_wall_scalar_grid", C.c_int, [_P, C.c_int, C.c_uint, _P]),
+    ("pgmg_boussinesq_stage_grid", C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_double,
+                                             C.c_double, C.c_double, C.c_double, _DP, C.c_double,
+                                             C.c_double, _DP, _P]),
     ("pgmg_ops_release", C.c_int, [_P]),
     ("pgmg_batch_config_default", C.c_int, [C.POINTER(PgmgBatchConfig), C.c_int]),
     ("pgmg_batch_cycle", C.c_int, [C.POINTER(PgmgBatchConfig), C.c_int, C.c_int, _P, _P,

@@ -1,6 +1,8 @@
 // pgmg_boussinesq.hip — buoyancy-driven flow (include/pgmg.h "Buoyancy-driven flow"; DESIGN.md
 // §4j): k_bouss_step, k_scalar_wall, pgmg_boussinesq_step and pgmg_boussinesq_time
-// (pgmg_boussinesq_grid and pgmg_wall_scalar_grid, on the caller's arrays: pgmg_ops.hip).
+// (pgmg_boussinesq_grid and pgmg_wall_scalar_grid, on the caller's arrays: pgmg_ops.hip), and
+// bouss_advance, the time loop pgmg_boussinesq_step shares with pgmg_boussinesq_step_rk
+// (pgmg_bouss_rk.hip).
 //
 // The vorticity transport of pgmg_vorticity.hip with a transported scalar T that feeds back:
 //     w_t + u w_x + v w_y = nu lap(w) + (by T_x - bx T_y),    T_t + u T_x + v T_y = kappa lap(T).
@@ -258,7 +260,7 @@ const char *scalar_wall_error(unsigned adiabatic)
 }
 
 // n doubles of zeroed, registered device memory (the entries' scratch arrays)
-static int bouss_alloc(pgmg_ctx *c, double **q, size_t n, const char *what)
+int bouss_alloc(pgmg_ctx *c, double **q, size_t n, const char *what)
 {
     if (*q) return PGMG_OK;
     if (hipMalloc((void **)q, n * sizeof(double)) != hipSuccess) {
@@ -270,25 +272,24 @@ static int bouss_alloc(pgmg_ctx *c, double **q, size_t n, const char *what)
     return PGMG_OK;
 }
 
-}  // namespace pgmg
-
-extern "C" {
-
-int pgmg_boussinesq_step(pgmg_ctx *c, const pgmg_solve_opts *o, double omega, const pgmg_bouss_params *p,
-                         double *d_T, int nsteps, pgmg_bouss_info *info)
+// pgmg_boussinesq_step (order 1) and pgmg_boussinesq_step_rk (pgmg_bouss_rk.hip): what they
+// refuse, then nsteps steps of `order` stages each (include/pgmg.h "Runge-Kutta buoyancy-driven
+// flow").  Stage 1 is the Euler pass; order 1 runs nothing else
+int bouss_advance(pgmg_ctx *c, const pgmg_solve_opts *o, double omega, const pgmg_bouss_params *p,
+                  double *d_T, int order, int nsteps, pgmg_bouss_info *info, const std::string &who)
 {
-    const std::string who("pgmg_boussinesq_step");
     if (!c || !o || !p || !d_T || !info) return set_err(PGMG_ERR_ARG, "null argument");
     if (const char *bad = solve_opts_error(*o)) return set_err(PGMG_ERR_ARG, who + ": " + bad);
     if (o->monitor & PGMG_MON_ERROR)
         return set_err(PGMG_ERR_ARG, who + ": PGMG_MON_ERROR needs the analytic problem; the "
                                            "right-hand side is the vorticity");
-    PGMG_TRY(damp_omega_check(omega, "pgmg_boussinesq_step"));
+    PGMG_TRY(damp_omega_check(omega, who.c_str()));
     if (const char *bad = vort_step_error(p->dt, p->nu)) return set_err(PGMG_ERR_ARG, who + ": " + bad);
     if (const char *bad = bouss_step_error(p->kappa, p->buoy)) return set_err(PGMG_ERR_ARG, who + ": " + bad);
     if (const char *bad = vort_wall_error(p->mode, p->walls)) return set_err(PGMG_ERR_ARG, who + ": " + bad);
     if (const char *bad = scalar_wall_error(p->adiabatic)) return set_err(PGMG_ERR_ARG, who + ": " + bad);
     if (nsteps < 1) return set_err(PGMG_ERR_ARG, who + ": nsteps must be at least 1");
+    if (order < 1 || order > 3) return set_err(PGMG_ERR_ARG, who + ": order must be 1, 2 or 3");
     if (!device_range(d_T, c->cfg.N)) return set_err(PGMG_ERR_ARG, who + ": T is not device memory");
     PGMG_TRY(vort_state_check(c, who));
     if (c->ext_phi)
@@ -308,51 +309,78 @@ int pgmg_boussinesq_step(pgmg_ctx *c, const pgmg_solve_opts *o, double omega, co
     // of the cycles' captured graphs, so the result is copied onto it), dense for T
     if (!c->vt_out.base) PGMG_TRY(alloc_grid(c->vt_out, L));
     PGMG_TRY(bouss_alloc(c, &c->bq_tout, elems, "pgmg_boussinesq_step's T grid"));
+    // the grids a Runge-Kutta step keeps the w and the T it started from in (order > 1 only)
+    if (order > 1) {
+        if (!c->vt_w0.base) PGMG_TRY(alloc_grid(c->vt_w0, L));
+        PGMG_TRY(bouss_alloc(c, &c->bq_t0, elems, "pgmg_boussinesq_step_rk's saved T"));
+    }
     PGMG_TRY(grad_reserve(c, gradient_blocks(N)));
     double *const total = c->grad_buf + c->grad_cap;
     double *const F = G<double>(L.F), *const out = G<double>(c->vt_out), *const tout = c->bq_tout;
+    double *const W0 = order > 1 ? G<double>(c->vt_w0) : nullptr, *const T0 = order > 1 ? c->bq_t0 : nullptr;
     PGMG_TRY(check_span(F, L.P, 8, 0, N - 1, 0, N - 1, "k_bouss_step w"));
     PGMG_TRY(check_span(out, L.P, 8, 0, N - 1, 0, N - 1, "k_bouss_step wout"));
     PGMG_TRY(check_span(tout, N, 8, 0, N - 1, 0, N - 1, "k_bouss_step tout"));
+    if (W0) {
+        PGMG_TRY(check_span(W0, L.P, 8, 0, N - 1, 0, N - 1, "k_bouss_stage w0"));
+        PGMG_TRY(check_span(T0, N, 8, 0, N - 1, 0, N - 1, "k_bouss_stage T0"));
+    }
     // (rows 0 .. N of a level-0 grid are one contiguous range: see pgmg_set_problem)
     const size_t bytes = (size_t)L.P * L.es * (size_t)N;
     // the context's stream starts after the caller's work on T
     PGMG_TRY(order_after_caller(c));
+    // the Shu-Osher coefficients (a, b) of stages 2 and 3, by order (stage 1 is the Euler pass)
+    const double K3 = 0x1.5555555555555p-2, B3 = 0x1.5555555555555p-1;
+    const double coef[4][2][2] = {{}, {}, {{0.5, 0.5}, {}}, {{0.75, 0.25}, {K3, B3}}};
     fl.worst_res = -1.0;
     double vmax = 0.0;
     for (int n = 0; n < nsteps; ++n) {
-        // 1. w's frame from the current psi and T's adiabatic walls; 2. the step, psi where it
-        // lies now (the cross-fused cycles rotate the grids), and its copies back onto f and T
-        const double *const psi = G<double>(L.A);
-        PGMG_TRY(check_span(psi, L.P, 8, 0, N - 1, 0, N - 1, "k_bouss_step psi"));
-        HIPC(hipEventRecord(c->vt_ev[0], c->s));
-        launch_vort_wall(psi, L.P, F, L.P, N, h, p->mode, p->walls, c->s);
-        launch_scalar_wall(d_T, N, N, p->adiabatic, c->s);
-        launch_bouss_step(psi, L.P, F, L.P, d_T, N, out, L.P, tout, N, N, h, dt, p->nu, p->kappa,
-                          p->buoy, c->grad_buf, total, c->s);
-        HIPC(hipGetLastError());
-        HIPC(hipMemcpyAsync(row_ptr(L.F, 0, L.P, L.es), row_ptr(c->vt_out, 0, L.P, L.es), bytes,
-                            hipMemcpyDeviceToDevice, c->s));
-        HIPC(hipMemcpyAsync(d_T, tout, elems * sizeof(double), hipMemcpyDeviceToDevice, c->s));
-        HIPC(hipEventRecord(c->vt_ev[1], c->s));
-        HIPC(hipMemcpyAsync(&vmax, total, sizeof(double), hipMemcpyDeviceToHost, c->s));
-        PGMG_TRY(set_problem_rhs_on_device(c));   // (waits for the stream)
-        float ms = 0.f;
-        HIPC(hipEventElapsedTime(&ms, c->vt_ev[0], c->vt_ev[1]));
-        fl.step_ms += ms;
-        // 3. the solve, warm-started from the previous psi
-        PGMG_TRY(pgmg_solve_damped(c, o, omega, &fl.last));
-        long long sweeps = 0;
-        PGMG_TRY(pgmg_stats(c, &sweeps, nullptr));
-        fl.steps = n + 1;
-        fl.cycles += fl.last.cycles;
-        fl.sweeps += sweeps;
-        fl.solve_ms += fl.last.elapsed_ms;
-        // (a NaN residual compares false: it takes the place of any finite one, and keeps it)
-        if (!(fl.last.res <= fl.worst_res) && !std::isnan(fl.worst_res)) {
-            fl.worst_res = fl.last.res;
-            fl.worst_reason = fl.last.reason;
+        for (int k = 0; k < order; ++k) {
+            // 1. w's frame from the current psi and T's adiabatic walls; 2. the stage, psi where
+            // it lies now (the cross-fused cycles rotate the grids), and its copies back onto f
+            // and T
+            const double *const psi = G<double>(L.A);
+            PGMG_TRY(check_span(psi, L.P, 8, 0, N - 1, 0, N - 1, "k_bouss_step psi"));
+            HIPC(hipEventRecord(c->vt_ev[0], c->s));
+            launch_vort_wall(psi, L.P, F, L.P, N, h, p->mode, p->walls, c->s);
+            launch_scalar_wall(d_T, N, N, p->adiabatic, c->s);
+            if (k == 0) {
+                if (W0) {
+                    HIPC(hipMemcpyAsync(row_ptr(c->vt_w0, 0, L.P, L.es), row_ptr(L.F, 0, L.P, L.es),
+                                        bytes, hipMemcpyDeviceToDevice, c->s));
+                    HIPC(hipMemcpyAsync(T0, d_T, elems * sizeof(double), hipMemcpyDeviceToDevice, c->s));
+                }
+                launch_bouss_step(psi, L.P, F, L.P, d_T, N, out, L.P, tout, N, N, h, dt, p->nu,
+                                  p->kappa, p->buoy, c->grad_buf, total, c->s);
+            } else {
+                launch_bouss_stage(psi, L.P, F, L.P, d_T, N, W0, L.P, T0, N, out, L.P, tout, N, N, h,
+                                   dt, p->nu, p->kappa, p->buoy, coef[order][k - 1][0],
+                                   coef[order][k - 1][1], c->grad_buf, total, c->s);
+            }
+            HIPC(hipGetLastError());
+            HIPC(hipMemcpyAsync(row_ptr(L.F, 0, L.P, L.es), row_ptr(c->vt_out, 0, L.P, L.es), bytes,
+                                hipMemcpyDeviceToDevice, c->s));
+            HIPC(hipMemcpyAsync(d_T, tout, elems * sizeof(double), hipMemcpyDeviceToDevice, c->s));
+            HIPC(hipEventRecord(c->vt_ev[1], c->s));
+            HIPC(hipMemcpyAsync(&vmax, total, sizeof(double), hipMemcpyDeviceToHost, c->s));
+            PGMG_TRY(set_problem_rhs_on_device(c));   // (waits for the stream)
+            float ms = 0.f;
+            HIPC(hipEventElapsedTime(&ms, c->vt_ev[0], c->vt_ev[1]));
+            fl.step_ms += ms;
+            // 3. the solve, warm-started from the previous psi
+            PGMG_TRY(pgmg_solve_damped(c, o, omega, &fl.last));
+            long long sweeps = 0;
+            PGMG_TRY(pgmg_stats(c, &sweeps, nullptr));
+            fl.cycles += fl.last.cycles;
+            fl.sweeps += sweeps;
+            fl.solve_ms += fl.last.elapsed_ms;
+            // (a NaN residual compares false: it takes the place of any finite one, and keeps it)
+            if (!(fl.last.res <= fl.worst_res) && !std::isnan(fl.worst_res)) {
+                fl.worst_res = fl.last.res;
+                fl.worst_reason = fl.last.reason;
+            }
         }
+        fl.steps = n + 1;
     }
     // the returned frames belong to the returned psi and T
     HIPC(hipEventRecord(c->vt_ev[0], c->s));
@@ -370,6 +398,16 @@ int pgmg_boussinesq_step(pgmg_ctx *c, const pgmg_solve_opts *o, double omega, co
     fl.elapsed_ms =
         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return PGMG_OK;
+}
+
+}  // namespace pgmg
+
+extern "C" {
+
+int pgmg_boussinesq_step(pgmg_ctx *c, const pgmg_solve_opts *o, double omega, const pgmg_bouss_params *p,
+                         double *d_T, int nsteps, pgmg_bouss_info *info)
+{
+    return bouss_advance(c, o, omega, p, d_T, 1, nsteps, info, "pgmg_boussinesq_step");
 }
 
 int pgmg_boussinesq_time(pgmg_ctx *c, int which, int reps, double *ms_per_pass, double *bytes)

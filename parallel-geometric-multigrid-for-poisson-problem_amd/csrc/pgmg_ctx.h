@@ -296,6 +296,12 @@ struct pgmg_ctx {
     // pgmg_boussinesq_time's five scratch arrays (N * N doubles each); registered allocations
     double *bq_tout = nullptr;
     double *bq_scr = nullptr;
+    // pgmg_boussinesq_step_rk (pgmg_bouss_rk.hip): the dense N x N grid that keeps the T a step
+    // started from, made on the first call with order > 1 (the w it started from goes into
+    // vt_w0), and pgmg_boussinesq_rk_time's seven scratch arrays (N * N doubles each); registered
+    // allocations
+    double *bq_t0 = nullptr;
+    double *bq_rk_scr = nullptr;
 };
 
 namespace pgmg {

@@ -158,7 +158,7 @@ int pgmg_destroy(pgmg_ctx *c)
     for (hipEvent_t e : c->vt_ev)
         if (e) (void)hipEventDestroy(e);
     free_grid(c->vt_w0);
-    for (double *q : {c->vt_rk_scr, c->bq_tout, c->bq_scr})
+    for (double *q : {c->vt_rk_scr, c->bq_tout, c->bq_scr, c->bq_t0, c->bq_rk_scr})
         if (q) {
             unregister_alloc(q);
             (void)hipFree(q);

@@ -151,6 +151,24 @@ void launch_bouss_step(const double *psi, long long Pp, const double *w, long lo
 void launch_scalar_wall(double *T, long long Pt, int N, unsigned adiabatic, hipStream_t s);
 const char *bouss_step_error(double kappa, const double buoy[2]);
 const char *scalar_wall_error(unsigned adiabatic);
+// *q = n doubles of zeroed, registered device memory unless it is set already (the scratch arrays
+// of the entries here and in pgmg_bouss_rk.hip; pgmg_destroy frees them)
+int bouss_alloc(pgmg_ctx *c, double **q, size_t n, const char *what);
+// the time loop of pgmg_boussinesq_step (order 1) and pgmg_boussinesq_step_rk: every refusal of
+// the two entries under the name `who`, then nsteps steps of `order` stages
+int bouss_advance(pgmg_ctx *c, const pgmg_solve_opts *o, double omega, const pgmg_bouss_params *p,
+                  double *d_T, int order, int nsteps, pgmg_bouss_info *info, const std::string &who);
+
+// --- pgmg_bouss_rk.hip
+// A Runge-Kutta stage in Shu-Osher form (include/pgmg.h "Runge-Kutta buoyancy-driven flow"), under
+// launch_bouss_step's conventions: wout = a * w0 + b * (the Euler step of w under psi and T) and
+// tout = a * T0 + b * (the Euler step of T) on the interior, w's and T's frames on the frames; w0
+// may be w and T0 may be T; vmax as in launch_vort_step.  No span checks here
+void launch_bouss_stage(const double *psi, long long Pp, const double *w, long long Pw, const double *T,
+                        long long Pt, const double *w0, long long Pw0, const double *T0, long long Pt0,
+                        double *wout, long long Pwo, double *tout, long long Pto, int N, double h,
+                        double dt, double nu, double kappa, const double buoy[2], double a, double b,
+                        double *partials, double *vmax, hipStream_t s);
 
 // --- pgmg_monitor.hip
 // the damping pass on a level of the FMG pyramid (no norm, nothing waits); fmg_damp_reserve

@@ -360,6 +360,48 @@ int pgmg_boussinesq_grid(const double *d_psi, const double *d_w, const double *d
     return PGMG_OK;
 }
 
+// wout = a * w0 + b * (the Euler step of w) and Tout = a * T0 + b * (the Euler step of T) on the
+// caller's arrays (pitch N): pgmg_boussinesq_step_rk's stage pass (pgmg_bouss_rk.hip); w0 may be
+// w and T0 may be T
+int pgmg_boussinesq_stage_grid(const double *d_psi, const double *d_w, const double *d_T,
+                               const double *d_w0, const double *d_T0, double *d_wout, double *d_Tout,
+                               int N, double h, double dt, double nu, double kappa,
+                               const double buoy[2], double a, double b, double *vmax, void *stream)
+{
+    const std::string who("pgmg_boussinesq_stage_grid");
+    int e = vort_op_check(who.c_str(), N, h);
+    if (e) return e;
+    if (const char *bad = vort_step_error(dt, nu)) return set_err(PGMG_ERR_ARG, who + ": " + bad);
+    if (const char *bad = bouss_step_error(kappa, buoy)) return set_err(PGMG_ERR_ARG, who + ": " + bad);
+    if (!std::isfinite(a) || !std::isfinite(b)) return set_err(PGMG_ERR_ARG, who + ": a and b must be finite");
+    if (!d_psi || !d_w || !d_T || !d_w0 || !d_T0 || !d_wout || !d_Tout)
+        return set_err(PGMG_ERR_ARG, who + ": null psi, w, T, w0, T0, wout or Tout");
+    const size_t bytes = (size_t)N * N * sizeof(double);
+    if (!device_range(d_wout, N) || !device_range(d_Tout, N))
+        return set_err(PGMG_ERR_ARG, who + ": an output is not device memory");
+    if (ranges_overlap(d_wout, bytes, d_Tout, bytes)) return set_err(PGMG_ERR_ARG, who + ": the outputs overlap");
+    for (const double *out : {d_wout, d_Tout})
+        for (const double *in : {d_psi, d_w, d_T, d_w0, d_T0})
+            if (ranges_overlap(out, bytes, in, bytes))
+                return set_err(PGMG_ERR_ARG, who + ": an output overlaps psi, w, T, w0 or T0");
+    hipStream_t s = (hipStream_t)stream;
+    OpScratch *op = nullptr;
+    if ((e = ensure_scratch(s, 0, &op))) return e;
+    const size_t np = (size_t)gradient_blocks(N);
+    if (vmax && (e = ensure_grad(s, *op, np + 1))) return e;
+    double *top = vmax ? op->grad + np : nullptr;
+    launch_bouss_stage(d_psi, N, d_w, N, d_T, N, d_w0, N, d_T0, N, d_wout, N, d_Tout, N, N, h, dt, nu,
+                       kappa, buoy, a, b, op->grad, top, s);
+    HIPC(hipGetLastError());
+    if (vmax) {
+        double t = 0.0;
+        HIPC(hipMemcpyAsync(&t, top, sizeof(t), hipMemcpyDeviceToHost, s));
+        HIPC(hipStreamSynchronize(s));
+        *vmax = t;
+    }
+    return PGMG_OK;
+}
+
 // T's adiabatic walls on the caller's array (pitch N): pgmg_boussinesq_step's scalar wall pass
 int pgmg_wall_scalar_grid(double *d_T, int N, unsigned adiabatic, void *stream)
 {
